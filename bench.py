@@ -10,17 +10,33 @@ collective: per-GPU work is fixed as N grows ("weak").  The timed region is
 bracketed by a barrier + device sync on both sides, and the max over ranks is
 taken.
 
-Rank 0 prints ONE JSON line (bench contract) with two extra objects:
+Rank 0 prints ONE JSON line (bench contract).  A plain run does what the
+headline figure needs and no more: it builds the shard, warms up, times
+--steps launches, writes the outputs when --dump-outputs is given, and prints
+the line, which also carries
   roofline      the dominant kernel's achieved algorithmic HBM bandwidth
-                (2L + 2S bytes per packet / avg kernel duration from HIP
-                events on the launch stream) vs 8 TB/s; `traffic` = HBM bytes
-                per launch from the rocprofv3 PMC pass committed under
+                (2L + 2S bytes per packet / avg kernel duration from the HIP
+                events that span the timed region) vs 8 TB/s; `traffic` = HBM
+                bytes per launch from the rocprofv3 PMC pass committed under
                 profiles/ (FETCH_SIZE x 2 + WRITE_SIZE, gfx950 correction), or
                 null when absent.
+--full adds everything that takes runs or checks of its own:
+  parity_spot_check  sampled packets of the output against the oracle;
+  roofline.kernel_min_us / kernel_median_us  launches timed one by one after
+                the timed region;
+  e2e           the host-staged batch on every rank (--no-e2e leaves it out);
   cpu_baseline  the CPU restatement (oracle/, "port": the Go reference cannot
                 be built here) on BASELINE configs[0]: 65,536 x 1200 B
                 Salamander obfuscate + deobfuscate round trips on the host
-                cores, rank 0 at N = 1 only.
+                cores, and cpu_path, the product's own CPU path on the same
+                workload; rank 0 at N = 1 only (--no-cpu-baseline leaves both
+                out).
+
+--dump-outputs DIR writes what the last timed launch left in the caller's
+output arrays as DIR/<name>.npy (float32): `out`, the output buffer's bytes,
+and `out_len`, the per-packet output lengths.  An array of more values than
+its share of the 64 MB budget is sampled at fixed, seeded positions.  The
+shard is seeded, so two runs with the same arguments see the same inputs.
 """
 from __future__ import annotations
 
@@ -55,9 +71,18 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="salamander-1m", choices=sorted(CONFIGS))
     ap.add_argument("--direction", default="obfuscate", choices=["obfuscate", "deobfuscate"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the parity spot "
+                         "check against the oracle, per-launch kernel times, the host-staged "
+                         "e2e batch and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output arrays to "
+                         "DIR/<name>.npy (float32; at most 64 MB, larger arrays sampled at "
+                         "fixed seeded positions)")
     ap.add_argument("--cpu-seconds", type=float, default=2.0,
-                    help="wall seconds of CPU-baseline sampling (x threads = CPU work)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: wall seconds of CPU-baseline sampling (x threads = CPU work)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: leave out cpu_baseline and cpu_path")
     ap.add_argument("--inproc", type=int, default=0,
                     help="in-process sharding: one process, K contexts over the visible GPUs "
                          "(context k on GPU k mod count), the config's batch cut by bytes "
@@ -111,8 +136,8 @@ def parse():
                     help="also time every mode of the host-staged path on rank 0 (pageable, "
                          "pinned, OUT_UNINIT, 2,048-B slots: e2e.modes)")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the all-ranks host-staged batch after the timed region "
-                         "(e2e.aggregate_gib_s / e2e.per_rank)")
+                    help="--full: skip the all-ranks host-staged batch after the timed "
+                         "region (e2e.aggregate_gib_s / e2e.per_rank)")
     return ap.parse_args()
 
 
@@ -247,6 +272,27 @@ def spot_check(torch, sh, kind, n, direction_out, saved, launches):
         if got != w:
             return False
     return bool((sh["out_len"].cpu().numpy() == lens + S).all())
+
+
+# --dump-outputs: values per array (float32: 40 MB in all, under the 64 MB cap)
+DUMP_VALUES = {"out": 8 << 20, "out_len": 2 << 20}
+
+
+def dump_outputs(torch, outdir, arrays, suffix=""):
+    """Write each (name, device tensor) as outdir/<name><suffix>.npy in
+    float32: the whole array when it has at most DUMP_VALUES[name] values,
+    else the values at that many positions drawn once from a seeded generator
+    (the same positions in every run of the same shape)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for k, (name, t) in enumerate(arrays):
+        t = t.reshape(-1)
+        cap = DUMP_VALUES[name]
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(7001 + k)
+            idx = torch.randint(0, t.numel(), (cap,), generator=g, dtype=torch.int64)
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), t.cpu().numpy().astype(np.float32))
 
 
 def kernel_name(kind: int, direction: int, multi: bool, ppw: int) -> str:
@@ -559,6 +605,10 @@ def inproc_bench(args):
     t0 = time.perf_counter()
     steps(args.steps)
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        for k, sh in enumerate(shs):
+            dump_outputs(torch, args.dump_outputs, [("out", sh["out"]), ("out_len", sh["out_len"])],
+                         f".shard{k}" if K > 1 else "")
     out = {"metric": f"GiB/s payload obfuscated, device-resident, {args.config}, "
                      f"{K} in-process shards (sqobfs_shard_launch, {depth} steps in flight)",
            "value": round(payload * args.steps / el / 2**30, 3), "unit": "GiB/s",
@@ -781,7 +831,7 @@ def main():
                               sh["out_len"], None, sh["psk_id"], flags=ob)
         alg_bytes = 2 * sh["payload_bytes"] + S * n
 
-    saved = save_samples(sh, n) if direction == sqobfs.OBFUSCATE else None
+    saved = save_samples(sh, n) if args.full and direction == sqobfs.OBFUSCATE else None
     warm, wt0 = 0, time.perf_counter()
     while warm < args.warmup or time.perf_counter() - wt0 < args.warmup_s:
         sqobfs.launch(ctx, kr, direction, b, s)
@@ -810,16 +860,23 @@ def main():
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     kern_avg_ms = e_beg.elapsed_time(e_end) / args.steps
-    # per-launch spread, after the timed region (not in `value`): each
-    # kernel's own dispatch records its event pair
-    n_each = min(args.steps, 20)
-    dev_ev = sqobfs.DispatchEvents(n_each)
-    for i in range(n_each):
-        dev_ev.arm(i)
-        sqobfs.launch(ctx, kr, direction, b, s)
-    torch.cuda.synchronize(dev)
-    kern_ms = sorted(dev_ev.elapsed_ms(i) for i in range(n_each))
-    dev_ev.close()
+    if args.dump_outputs:
+        # what the last timed launch left in the caller's arrays
+        dump_outputs(torch, args.dump_outputs,
+                     [("out", sh["out"] if direction == sqobfs.OBFUSCATE else back),
+                      ("out_len", sh["out_len"])], f".rank{rank}" if world > 1 else "")
+    n_each, kern_ms = 0, None
+    if args.full:
+        # per-launch spread, after the timed region (not in `value`): each
+        # kernel's own dispatch records its event pair
+        n_each = min(args.steps, 20)
+        dev_ev = sqobfs.DispatchEvents(n_each)
+        for i in range(n_each):
+            dev_ev.arm(i)
+            sqobfs.launch(ctx, kr, direction, b, s)
+        torch.cuda.synchronize(dev)
+        kern_ms = sorted(dev_ev.elapsed_ms(i) for i in range(n_each))
+        dev_ev.close()
 
     tdev = dev if args.dist_backend == "nccl" else torch.device("cpu")
     if dist:
@@ -827,24 +884,25 @@ def main():
         kern_avg_ms = max_over_ranks(torch, dist, kern_avg_ms, tdev)
 
     parity = None
-    if args.device_salt:
-        # the last launch's salts, from the oracle's ChaCha20 (checker only)
-        import numpy as np
-        import oracle_lib as ol
-        last = ctx.salt_seq - 1
-        salts = np.frombuffer(ol.device_salts(SALT_KEY, last, n, S), np.uint8)
-        sh["salt"] = torch.from_numpy(salts.copy()).to(dev)
-    if direction == sqobfs.OBFUSCATE:
-        parity = spot_check(torch, sh, kind, n, sh["out"], saved, warm + args.steps + n_each)
-    else:
-        lens = sh["lens"].cpu().numpy()
-        offs = sh["in_off"].cpu().numpy()
-        boffs = back_off.cpu().numpy()
-        parity = all(torch.equal(back[int(boffs[i]):int(boffs[i]) + int(lens[i])],
-                                 sh["data"][int(offs[i]):int(offs[i]) + int(lens[i])])
-                     for i in sorted(set([0, n - 1] + list(range(0, n, 4099)))))
-    if dist:
-        parity = -max_over_ranks(torch, dist, -1.0 if parity else 0.0, tdev) > 0
+    if args.full:
+        if args.device_salt:
+            # the last launch's salts, from the oracle's ChaCha20 (checker only)
+            import numpy as np
+            import oracle_lib as ol
+            last = ctx.salt_seq - 1
+            salts = np.frombuffer(ol.device_salts(SALT_KEY, last, n, S), np.uint8)
+            sh["salt"] = torch.from_numpy(salts.copy()).to(dev)
+        if direction == sqobfs.OBFUSCATE:
+            parity = spot_check(torch, sh, kind, n, sh["out"], saved, warm + args.steps + n_each)
+        else:
+            lens = sh["lens"].cpu().numpy()
+            offs = sh["in_off"].cpu().numpy()
+            boffs = back_off.cpu().numpy()
+            parity = all(torch.equal(back[int(boffs[i]):int(boffs[i]) + int(lens[i])],
+                                     sh["data"][int(offs[i]):int(offs[i]) + int(lens[i])])
+                         for i in sorted(set([0, n - 1] + list(range(0, n, 4099)))))
+        if dist:
+            parity = -max_over_ranks(torch, dist, -1.0 if parity else 0.0, tdev) > 0
 
     total_payload = sh["payload_bytes"] * args.steps
     if dist:
@@ -912,16 +970,18 @@ def main():
             "kernel_avg_us": round(kern_avg_ms * 1e3, 2),
             "kernel_avg_rule": "HIP events spanning the timed region's back-to-back "
                                "launches / steps (dispatch gaps included)",
-            "kernel_min_us": round(kern_ms[0] * 1e3, 2),
-            "kernel_median_us": round(kern_ms[len(kern_ms) // 2] * 1e3, 2),
-            "kernel_each_rule": f"{n_each} launches after the timed region, each timed by "
-                                "its own dispatch (sqobfs_debug_time_next_launch)",
             "algorithmic_bytes_per_launch": alg_bytes,
             "bytes_rule": "obfuscate 2L+2S per packet (2L+S with device salts), "
                           "deobfuscate 2L+S (SURVEY.md 8(d))",
         },
-        "parity_spot_check": parity,
     }
+    if args.full:
+        out["roofline"].update({
+            "kernel_min_us": round(kern_ms[0] * 1e3, 2),
+            "kernel_median_us": round(kern_ms[len(kern_ms) // 2] * 1e3, 2),
+            "kernel_each_rule": f"{n_each} launches after the timed region, each timed by "
+                                "its own dispatch (sqobfs_debug_time_next_launch)"})
+        out["parity_spot_check"] = parity
     if pmc:
         out["roofline"]["traffic_source"] = pmc.get("source")
     cf = copy_at_footprint(args.config) if args.layout == "dense" and not args.packets else None
@@ -930,7 +990,7 @@ def main():
         out["roofline"]["frac_of_copy_at_footprint"] = round(achieved / PEAK_HBM_GBS / cf["copy_frac"], 4)
     if args.latency and rank == 0:
         out["latency"] = latency_bench()
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         # every rank at once, behind a barrier, after the timed region (not in
         # `value`): the host-staged rate of the whole job
         out["e2e"] = e2e_all_ranks(torch, sqobfs, ctx, kr, kind, dist, tdev, world)
@@ -951,7 +1011,7 @@ def main():
             out["udp_quic_e2e"] = [udp_quic_rate(sqobfs, ctx, kr, (L or 758) + 11, batch=bt,
                                                  suite=su)
                                    for su in (0, 1) for bt in (256, 1024)]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         out["cpu_path"] = cpu_path_rate()
     if rank == 0:

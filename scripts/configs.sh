@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-cfg}; mkdir -p $O
-run() { timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline "$@"; }
+run() { timeout -k 10 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline "$@"; }
 for c in salamander-1m xplus-1m salamander-ragged-4m salamander-16m-256psk; do
   for d in obfuscate deobfuscate; do
     run --config $c --direction $d > $O/${c}_$d.json 2> $O/err.txt || { tail -5 $O/err.txt; exit 1; }

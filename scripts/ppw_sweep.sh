@@ -8,7 +8,7 @@ mkdir -p $O
 for r in $(seq 1 ${REPS:-3}); do
   for c in "$@"; do
     for w in $PPWS; do
-      SQOBFS_TUNE_PPW=$w timeout -k 10 120 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --config $c > $O/${c}_p${w}_r$r.json 2> $O/err.txt || { echo "$c ppw $w FAILED"; tail -5 $O/err.txt; exit 1; }
+      SQOBFS_TUNE_PPW=$w timeout -k 10 120 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --config $c > $O/${c}_p${w}_r$r.json 2> $O/err.txt || { echo "$c ppw $w FAILED"; tail -5 $O/err.txt; exit 1; }
     done
   done
   echo "pass $r done"

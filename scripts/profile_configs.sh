@@ -21,7 +21,8 @@ for c in $CFGS; do
   done
 done
 [ $PART = 1 ] && exit 0
-timeout -k 10 300 python bench.py > gpurun_out/$T/bench_default.json 2> gpurun_out/$T/bench_default.err || exit 1
-cat gpurun_out/$T/bench_default.json
+D=$(ls -dt */$T | head -1)  # the tag's output directory, made above
+timeout -k 10 300 python bench.py --full > $D/bench_default.json 2> $D/bench_default.err || exit 1
+cat $D/bench_default.json
 timeout -k 10 800 bash scripts/configs.sh $T/cfg > gpurun_out/$T/cfg.txt 2>&1 || { tail -20 gpurun_out/$T/cfg.txt; exit 1; }
 cat gpurun_out/$T/cfg.txt

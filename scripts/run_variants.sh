@@ -7,7 +7,7 @@ REPS=${REPS:-3}
 for r in $(seq 1 $REPS); do
   for L in build/var/lib_*.so; do
     n=$(basename $L .so)
-    SQOBFS_LIB=$L timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline "$@" > $O/${n}_r$r.json 2> $O/$n.err || { echo "$n FAILED"; tail -3 $O/$n.err; exit 1; }
+    SQOBFS_LIB=$L timeout -k 10 200 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline "$@" > $O/${n}_r$r.json 2> $O/$n.err || { echo "$n FAILED"; tail -3 $O/$n.err; exit 1; }
   done
 done
 python - "$O" <<'PY'

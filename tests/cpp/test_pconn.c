@@ -979,6 +979,7 @@ static void t_load(void) {
   int loaded = 0;
   uint32_t pm_max = 0, ns_min = 0xFFFFFFFFu;
   const double t0 = now_s();
+  const uint32_t seq0 = seq;
   while (now_s() - t0 < 0.5) {
     for (int j = 0; j < 256; j++, seq++) {
       load_payload(seq, pay);
@@ -989,6 +990,7 @@ static void t_load(void) {
     if (ei.load_permille > pm_max) pm_max = ei.load_permille;
     if (ei.cpu_ns_per_kib < ns_min) ns_min = ei.cpu_ns_per_kib;
   }
+  const double t_sus = now_s() - t0;
   sleep_ms(50);
   CHECK(sqobfs_pconn_stats_get(pc, &s2));
   const uint64_t nb = s2.tx_batches - s1.tx_batches, nc = s2.cpu_batches - s1.cpu_batches;
@@ -996,8 +998,23 @@ static void t_load(void) {
    * offer bulk load: there the load mode is not required to turn on) */
   CHECK(sqobfs_engine_info_get(g_ctx, &ei));
   const int slow = ei.cpu_ns_per_kib > 1500;
-  EXPECT(loaded || slow, "sustained load never turned the engine's load mode on (peak %u permille)",
-         pm_max);
+  /* the load mode turns on at a demand of 100 permille of a core: the
+   * datagrams' estimated CPU-path time per wall second, smoothed over 10 ms
+   * windows as (old + 3 new) / 4.  The writer is held to what the loopback
+   * stack takes, so on a busy host with a fast CPU path it may offer less
+   * (one clean run: peak 85 permille), and the engine is then right to stay
+   * out of the mode.  What the phase offered at the least, from the test's
+   * own count at the lowest CPU-path rate the phase saw, is a lower bound
+   * of the engine's figure; the smoothed value's peak is at least its mean
+   * over the phase, the mean of the windows less the ramp of the first few
+   * (under a tenth over 50 windows): from 110 permille offered, the mode
+   * must have turned on */
+  if (ns_min > ei.cpu_ns_per_kib) ns_min = ei.cpu_ns_per_kib;
+  const double offered_pm =
+      (double)(seq - seq0) * (1350 + 1024) / 1024.0 * ns_min / (t_sus * 1e9) * 1000.0;
+  EXPECT(loaded || slow || offered_pm < 110.0,
+         "sustained load never turned the engine's load mode on (peak %u permille, at least %.0f "
+         "offered)", pm_max, offered_pm);
   /* loaded, a batch of more than 64 launches when its CPU-path time exceeds
    * a launch's host cost: the phase's largest batch must have launched when
    * it clearly did (x1.5, and the CPU path's lowest rate seen in the phase:

@@ -34,7 +34,7 @@ def test_header_is_plain_c():
     assert out.returncode == 0, out.stderr
 
 
-def test_batch_struct_layout_matches_header():
+def test_batch_struct_layout_matches_header(tmp_path):
     """ctypes mirror of sqobfs_batch has the C layout (offsetof via gcc)."""
     prog = r'''
 #include <stdio.h>
@@ -43,7 +43,7 @@ def test_batch_struct_layout_matches_header():
 int main(void){printf("%zu %zu %zu %zu %zu\n", sizeof(sqobfs_batch),
  offsetof(sqobfs_batch,in), offsetof(sqobfs_batch,out_len), offsetof(sqobfs_batch,psk_id),
  offsetof(sqobfs_batch,in_cap));return 0;}'''
-    exe = "/tmp/sq_layout_probe"
+    exe = str(tmp_path / "sq_layout_probe")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(REPO, "include"), "-o", exe],
                    input=prog, text=True, check=True)
     got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True).stdout.split()]
@@ -52,7 +52,7 @@ int main(void){printf("%zu %zu %zu %zu %zu\n", sizeof(sqobfs_batch),
                    B.in_cap.offset]
 
 
-def test_engine_info_layout_matches_header():
+def test_engine_info_layout_matches_header(tmp_path):
     """ctypes mirror of sqobfs_engine_info has the C layout (round 5 grew it:
     load routing, affinity and the coalesced-launch counters; round 6, ABI 6:
     the completer's counters)."""
@@ -61,7 +61,7 @@ def test_engine_info_layout_matches_header():
     prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "sqobfs.h"\n'
             'int main(void){printf("%zu' + ' %zu' * len(fields) + '\\n", sizeof(sqobfs_engine_info)'
             + "".join(f", offsetof(sqobfs_engine_info,{f})" for f in fields) + ");return 0;}")
-    exe = "/tmp/sq_engine_info_probe"
+    exe = str(tmp_path / "sq_engine_info_probe")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(REPO, "include"), "-o", exe],
                    input=prog, text=True, check=True)
     got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True).stdout.split()]

@@ -37,7 +37,7 @@ def test_bench_two_ranks(config, packets, scaling, launcher):
            "--master-addr", "127.0.0.1", "--master-port", str(free_port())] \
         if launcher == "torchrun" else [sys.executable]
     cmd = pre + [os.path.join(REPO, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-           "--steps", "3", "--warmup", "1", "--warmup-s", "0", "--no-cpu-baseline",
+           "--steps", "3", "--warmup", "1", "--warmup-s", "0", "--full", "--no-cpu-baseline",
            "--config", config, "--packets", str(packets)]
     env = dict(os.environ, OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=110)
@@ -64,10 +64,10 @@ def test_bench_two_ranks(config, packets, scaling, launcher):
 
 
 def test_bench_one_rank_carries_e2e_and_no_e2e_skips_it():
-    """The default N = 1 line carries the host-staged e2e key (one rank);
+    """The --full N = 1 line carries the host-staged e2e key (one rank);
     --no-e2e leaves it out."""
     base = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1",
-            "--warmup-s", "0", "--no-cpu-baseline", "--packets", "65536"]
+            "--warmup-s", "0", "--full", "--no-cpu-baseline", "--packets", "65536"]
     for extra, want in (([], True), (["--no-e2e"], False)):
         r = subprocess.run(base + extra, cwd=REPO, capture_output=True, text=True, timeout=110)
         assert r.returncode == 0, r.stderr[-3000:]

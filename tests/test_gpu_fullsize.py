@@ -172,7 +172,7 @@ def test_bench_two_ranks_share_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--dist-backend", "gloo", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--config", "salamander-16m-256psk"]
+           "--full", "--no-cpu-baseline", "--config", "salamander-16m-256psk"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")][-1]
