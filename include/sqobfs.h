@@ -284,8 +284,8 @@ int sqobfs_host_alloc(sqobfs_ctx *ctx, size_t bytes, void **out);
 void sqobfs_host_free(sqobfs_ctx *ctx, void *p);
 
 /* ------------------------------------------------------------------------
- * QUIC packet protection: AEAD_CHACHA20_POLY1305
- * and AEAD_AES_128_GCM, each with its header protection.
+ * QUIC packet protection: AEAD_CHACHA20_POLY1305,
+ * AEAD_AES_128_GCM and AEAD_AES_256_GCM, each with its header protection.
  *
  * The next per-datagram byte transform under the obfuscation layer: quic-go
  * (v0.52.0-beta.1, go.mod:7; not in the reference tree) seals every 1-RTT
@@ -305,12 +305,15 @@ void sqobfs_host_free(sqobfs_ctx *ctx, void *p);
  * AES-128-GCM (TLS_AES_128_GCM_SHA256) is the same with
  *          payload -> AES-128-GCM(key, nonce, aad = header)   (SP 800-38D)
  *          mask = AES-128-ECB(hp, sample)                  (RFC 9001 5.4.3)
+ * AES-256-GCM (TLS_AES_256_GCM_SHA384) is AES-128-GCM with AES-256 in both
+ *          places: 32-byte key and hp, everything else unchanged.
  * The packet-number length is (first byte & 3) + 1 of the unprotected
  * header, as QUIC encodes it. */
 
 /* One connection's 1-RTT keys (from the TLS key schedule: "quic key",
  * "quic iv", "quic hp", RFC 9001 5.1).  AES-128-GCM uses key[0..16) and
- * hp[0..16). */
+ * hp[0..16); AES-256-GCM uses key[0..32) and hp[0..32), as
+ * ChaCha20-Poly1305 does. */
 typedef struct sqobfs_quic_key {
   uint8_t key[32];
   uint8_t iv[12];
@@ -320,6 +323,7 @@ typedef struct sqobfs_quic_key {
 /* Cipher suites (the AEAD of the negotiated TLS 1.3 suite, RFC 9001 5.3) */
 #define SQOBFS_QUIC_CHACHA20_POLY1305 0u /* TLS_CHACHA20_POLY1305_SHA256 */
 #define SQOBFS_QUIC_AES_128_GCM 1u       /* TLS_AES_128_GCM_SHA256 */
+#define SQOBFS_QUIC_AES_256_GCM 2u       /* TLS_AES_256_GCM_SHA384 */
 
 typedef struct sqobfs_quic_keyring sqobfs_quic_keyring;
 
@@ -354,8 +358,9 @@ typedef struct sqobfs_quic_batch {
 
 /* A keyring holds connections of ONE suite (a batch is sealed / opened
  * with the keyring's suite).  sqobfs_quic_keyring_create is the
- * ChaCha20-Poly1305 form.  For AES-128-GCM the key schedules and the GHASH
- * tables (about 16.5 KiB per connection) are prepared here, once. */
+ * ChaCha20-Poly1305 form.  For AES-128-GCM and AES-256-GCM the key
+ * schedules and the GHASH tables (about 16.5 KiB per connection) are
+ * prepared here, once.  Any other suite: SQ_EINVAL. */
 int sqobfs_quic_keyring_create_suite(sqobfs_ctx *ctx, uint32_t suite, uint32_t count,
                                      const sqobfs_quic_key *keys, sqobfs_quic_keyring **out);
 int sqobfs_quic_keyring_create(sqobfs_ctx *ctx, uint32_t count, const sqobfs_quic_key *keys,
@@ -382,7 +387,7 @@ int sqobfs_quic_open(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
  *         SQOBFS_QUIC_E* code; datagrams shorter than the salt give
  *         SQOBFS_QUIC_ESHORT).  In place (out_off == in_off) works.
  * okr: a Salamander keyring (entry 0 is the connection's PSK); kr: a QUIC
- * keyring of either suite. */
+ * keyring of any suite. */
 int sqobfs_quic_seal_salamander(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
                                 const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
                                 const uint8_t *salt, void *stream);
@@ -438,7 +443,7 @@ size_t sqobfs_host_staging_bytes(const sqobfs_ctx *ctx);
 /* Test hook: the next sqobfs_run_host whose pipeline reaches chunk `chunk`
  * fails there with SQ_EDEVICE, as a failed launch would (-1 = off). */
 void sqobfs_debug_fail_chunk(int chunk);
-/* Test hook: on != 0 makes multi-key AES-128-GCM launches skip the grouping
+/* Test hook: on != 0 makes multi-key AES-GCM launches skip the grouping
  * by key (the path taken when the grouping scratch cannot be allocated). */
 void sqobfs_debug_gcm_ungrouped(int on);
 /* Test hook: keyring tables (obfuscation and QUIC) and the AES-GCM grouping

@@ -155,9 +155,9 @@ struct sqobfs_quic_keyring {
   uint32_t count = 0;
   sq::QuicKeyDev *table = nullptr;  // device (ChaCha20-Poly1305)
   sq::QuicKeyDev host0;             // entry 0, passed by value
-  sq::QuicGcmKeyDev *gtable = nullptr;  // device (AES-128-GCM)
+  sq::QuicGcmKeyDev *gtable = nullptr;  // device (AES-128-GCM, AES-256-GCM)
   uint32_t *t0 = nullptr;               // device AES T-table (256 words)
-  uint32_t grk0[44], ghrk0[44], giv0[3];
+  uint32_t grk0[sq::kGcmRkWords], ghrk0[sq::kGcmRkWords], giv0[3];
 };
 
 // sqobfs_shard_launch: one completion event per context of the step
@@ -1011,9 +1011,10 @@ int sqobfs_xplus_deobfuscate(sqobfs_ctx *ctx, const sqobfs_keyring *kr, const sq
 
 // ---------------------------------------------------------------- QUIC
 
-// ---- AES-128-GCM key preparation (host, once per keyring): FIPS-197 key
-// expansion, H = AES_K(0^128), and the 4-bit GHASH tables of H^1..H^128
-// that sq_quic_gcm.hip reads.  Connection setup work, not per packet.
+// ---- AES-GCM key preparation (host, once per keyring): FIPS-197 key
+// expansion (AES-128 or AES-256), H = AES_K(0^128), and the 4-bit GHASH
+// tables of H^1..H^128 that sq_quic_gcm.hip reads.  Connection setup work,
+// not per packet.
 extern "C++" {
 namespace {
 uint8_t gf8_mul(uint8_t a, uint8_t b) {
@@ -1075,18 +1076,43 @@ void aes128_expand(const uint8_t key[16], uint32_t rk[44]) {
   for (int i = 0; i < 44; i++) rk[i] = le32(w + 4 * i);
 }
 
-// one block, same column-word form as the device
-void aes128_block(const uint32_t rk[44], const uint8_t in[16], uint8_t out[16]) {
+// FIPS-197 5.2 with Nk = 8: 15 round keys; besides the RotWord / SubWord /
+// Rcon step at every eighth word, a plain SubWord at i mod 8 == 4
+void aes256_expand(const uint8_t key[32], uint32_t rk[60]) {
+  const uint8_t *sb = aes_tables().sbox;
+  uint8_t w[240];
+  memcpy(w, key, 32);
+  uint8_t rcon = 1;
+  for (int i = 8; i < 60; i++) {
+    uint8_t t[4] = {w[4 * i - 4], w[4 * i - 3], w[4 * i - 2], w[4 * i - 1]};
+    if (i % 8 == 0) {
+      const uint8_t t0 = t[0];
+      t[0] = (uint8_t)(sb[t[1]] ^ rcon);
+      t[1] = sb[t[2]];
+      t[2] = sb[t[3]];
+      t[3] = sb[t0];
+      rcon = gf8_mul(rcon, 2);
+    } else if (i % 8 == 4) {
+      for (int k = 0; k < 4; k++) t[k] = sb[t[k]];
+    }
+    for (int k = 0; k < 4; k++) w[4 * i + k] = w[4 * i - 32 + k] ^ t[k];
+  }
+  for (int i = 0; i < 60; i++) rk[i] = le32(w + 4 * i);
+}
+
+// one block under a schedule of nr + 1 round keys (nr = 10 or 14), same
+// column-word form as the device
+void aes_block(const uint32_t *rk, int nr, const uint8_t in[16], uint8_t out[16]) {
   const uint32_t *T = aes_tables().t0;
   auto rot = [](uint32_t x, int n) { return (x << n) | (x >> (32 - n)); };
   uint32_t s[4];
   for (int c = 0; c < 4; c++) s[c] = le32(in + 4 * c) ^ rk[c];
-  for (int r = 1; r <= 10; r++) {
+  for (int r = 1; r <= nr; r++) {
     uint32_t t[4];
     for (int c = 0; c < 4; c++) {
       const uint32_t a0 = T[s[c] & 0xFF], a1 = T[(s[(c + 1) & 3] >> 8) & 0xFF];
       const uint32_t a2 = T[(s[(c + 2) & 3] >> 16) & 0xFF], a3 = T[s[(c + 3) & 3] >> 24];
-      t[c] = r < 10 ? a0 ^ rot(a1, 8) ^ rot(a2, 16) ^ rot(a3, 24)
+      t[c] = r < nr ? a0 ^ rot(a1, 8) ^ rot(a2, 16) ^ rot(a3, 24)
                     : ((a0 >> 8) & 0xFF) | (a1 & 0xFF00) | ((a2 << 8) & 0xFF0000) |
                           ((a3 << 16) & 0xFF000000u);
       t[c] ^= rk[4 * r + c];
@@ -1128,17 +1154,26 @@ G128 g_mul(G128 x, G128 y) {  // SP 800-38D Algorithm 1
   return z;
 }
 
-void gcm_key(const sqobfs_quic_key &k, sq::QuicGcmKeyDev &d) {
+// AES rounds of a GCM suite
+int gcm_rounds(uint32_t suite) { return suite == SQOBFS_QUIC_AES_256_GCM ? 14 : 10; }
+
+void gcm_key(uint32_t suite, const sqobfs_quic_key &k, sq::QuicGcmKeyDev &d) {
   memset(&d, 0, sizeof d);
-  aes128_expand(k.key, d.rk);
-  aes128_expand(k.hp, d.hrk);
+  const int nr = gcm_rounds(suite);
+  if (nr == 14) {
+    aes256_expand(k.key, d.rk);
+    aes256_expand(k.hp, d.hrk);
+  } else {
+    aes128_expand(k.key, d.rk);
+    aes128_expand(k.hp, d.hrk);
+  }
   for (int i = 0; i < 3; i++) d.iv[i] = le32(k.iv + 4 * i);
   const uint8_t zero[16] = {0};
   uint8_t hb[16];
-  aes128_block(d.rk, zero, hb);
-  // rounds 1-9 stored rotated by 16 bits: the kernel folds the round key
+  aes_block(d.rk, nr, zero, hb);
+  // rounds 1..nr-1 stored rotated by 16 bits: the kernel folds the round key
   // under its rotl16 (sq_quic_gcm.hip aes_encrypt_n)
-  for (int i = 4; i < 40; i++) {
+  for (int i = 4; i < 4 * nr; i++) {
     d.rk[i] = (d.rk[i] >> 16) | (d.rk[i] << 16);
     d.hrk[i] = (d.hrk[i] >> 16) | (d.hrk[i] << 16);
   }
@@ -1197,7 +1232,8 @@ int sqobfs_quic_keyring_create_suite(sqobfs_ctx *ctx, uint32_t suite, uint32_t c
                                      const sqobfs_quic_key *keys, sqobfs_quic_keyring **out) {
   if (out) *out = nullptr;
   if (!ctx || !out || count == 0 || !keys) return SQ_EINVAL;
-  if (suite != SQOBFS_QUIC_CHACHA20_POLY1305 && suite != SQOBFS_QUIC_AES_128_GCM)
+  if (suite != SQOBFS_QUIC_CHACHA20_POLY1305 && suite != SQOBFS_QUIC_AES_128_GCM &&
+      suite != SQOBFS_QUIC_AES_256_GCM)
     return SQ_EINVAL;
   DeviceScope ds_(ctx->device);
   if (ds_.status != SQ_OK) return ds_.status;
@@ -1223,7 +1259,7 @@ int sqobfs_quic_keyring_create_suite(sqobfs_ctx *ctx, uint32_t suite, uint32_t c
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   } else {
     std::vector<sq::QuicGcmKeyDev> h(count);
-    for (uint32_t k = 0; k < count; k++) gcm_key(keys[k], h[k]);
+    for (uint32_t k = 0; k < count; k++) gcm_key(suite, keys[k], h[k]);
     memcpy(kr->grk0, h[0].rk, sizeof kr->grk0);
     memcpy(kr->ghrk0, h[0].hrk, sizeof kr->ghrk0);
     memcpy(kr->giv0, h[0].iv, sizeof kr->giv0);
@@ -1277,7 +1313,7 @@ static int quic_launch(int open, sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
     return SQ_EINVAL;
   DeviceScope ds_(ctx->device);
   if (ds_.status != SQ_OK) return ds_.status;
-  if (kr->suite == SQOBFS_QUIC_AES_128_GCM) {
+  if (kr->suite == SQOBFS_QUIC_AES_128_GCM || kr->suite == SQOBFS_QUIC_AES_256_GCM) {
     sq::QGParams g;
     memset(&g, 0, sizeof g);
     g.in = b->in;
@@ -1294,6 +1330,7 @@ static int quic_launch(int open, sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
     g.t0 = kr->t0;
     g.n = b->n;
     g.n_keys = kr->count;
+    g.nr = (uint32_t)gcm_rounds(kr->suite);
     memcpy(g.rk0, kr->grk0, sizeof g.rk0);
     memcpy(g.hrk0, kr->ghrk0, sizeof g.hrk0);
     memcpy(g.iv0, kr->giv0, sizeof g.iv0);

@@ -117,9 +117,9 @@ struct QParams {
   PskEntry opsk;         // the Salamander keyring's entry 0
 };
 
-// AES-128-GCM (TLS_AES_128_GCM_SHA256) connection keys on the device:
-// AES-128 key schedules of the payload key and the header-protection key as
-// little-endian column words (word 4r + c = bytes 4c..4c+3 of round key r),
+// AES-GCM (TLS_AES_128_GCM_SHA256, TLS_AES_256_GCM_SHA384) connection keys on
+// the device: AES key schedules of the payload key and the header-protection
+// key as little-endian column words (word 4r + c = bytes 4c..4c+3 of round key r),
 // the IV, per-position tables of H (hpos[j][n] = n x^(4 (31 - j)) H: X * H is
 // the XOR of hpos[j][nibble j of X], 32 independent lookups, no shifts), and
 // 4-bit GHASH tables of H^4, H^8, .. H^(4 kGcmPow4) (Shoup's method; slot
@@ -129,17 +129,25 @@ struct QParams {
 // power of H^4.
 constexpr uint32_t kGcmPow = 128;  // payload blocks of the cooperative pass (2,048 B)
 constexpr uint32_t kGcmPow4 = kGcmPow / 4;
+// One entry layout and one kernarg layout for both key sizes: the schedules
+// are sized for AES-256 (15 round keys, 60 words) and AES-128 uses the first
+// 44 words.  Templating the structs on the round count would save an
+// AES-128 entry 128 B of its 16.5 KiB and its kernarg 128 B that no kernel
+// loads (the kernels read round keys by index, never the whole array), and
+// would double the keyring, grouping and launch code that handles them.
+constexpr uint32_t kGcmRkWords = 60;
 struct QuicGcmKeyDev {
-  uint32_t rk[44];   // AES-128 key schedule, words 4..39 (rounds 1-9) rotated
-  uint32_t hrk[44];  // by 16 bits (sq_quic_gcm.hip aes_encrypt_n); hrk: the HP key's
+  uint32_t rk[kGcmRkWords];   // AES key schedule, rounds 1..NR-1 rotated by 16
+  uint32_t hrk[kGcmRkWords];  // bits (sq_quic_gcm.hip aes_encrypt_n); hrk: the HP key's
   uint32_t iv[3];
   uint32_t pad;
   uint32_t hpos[32][16][4];
   uint32_t htab[kGcmPow4][16][4];
 };
 
-// AES-128-GCM launch; rk0 / hrk0 / iv0 = keyring entry 0 (kernarg); t0 = the
-// 256-word AES T-table (device, 1 KiB), staged into LDS by every block.
+// AES-GCM launch; rk0 / hrk0 / iv0 = keyring entry 0 (kernarg); t0 = the
+// 256-word AES T-table (device, 1 KiB), staged into LDS by every block;
+// nr = the keyring's AES round count (10 or 14: picks the kernel).
 struct QGParams {
   const uint8_t *in;
   const uint64_t *in_off;
@@ -157,11 +165,12 @@ struct QGParams {
   const uint32_t *t0;
   uint32_t n;
   uint32_t n_keys;
-  uint32_t rk0[44];
-  uint32_t hrk0[44];
+  uint32_t rk0[kGcmRkWords];
+  uint32_t hrk0[kGcmRkWords];
   uint32_t iv0[3];
   uint32_t obfs;         // 1: fused Salamander layer (as QParams)
   const uint8_t *osalt;  // seal: [n*8] salts (device)
+  uint32_t nr;           // AES rounds: 10 or 14
   PskEntry opsk;         // the Salamander keyring's entry 0
 };
 
@@ -214,7 +223,7 @@ void sq_engine_ctx_closed(sqobfs_ctx *ctx);
 
 // launchers implemented in sq_quic_gcm.hip
 extern "C" int sq_launch_quic_gcm(int open, const sq::QGParams *qp, void *stream);
-// Multi-key AES-128-GCM batches: the packet permutation that groups them by
+// Multi-key AES-GCM batches (either key size): the packet permutation that groups them by
 // key (stable counting sort) and the per-key step table of the staged
 // kernel; packets with an out-of-range key id are rejected there (out_len,
 // pn_out) and take no step.  sq_gcm_group_scratch: the device scratch it

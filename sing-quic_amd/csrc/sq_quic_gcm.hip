@@ -1,17 +1,22 @@
 // sq_quic_gcm.hip -- gfx950 QUIC packet protection, TLS_AES_128_GCM_SHA256
-// (the suite every QUIC stack must implement).
+// (the suite every QUIC stack must implement) and
+// TLS_AES_256_GCM_SHA384.
 //
 // Replaces, for a whole ragged batch per launch, quic-go's per-packet
-//   internal/handshake/aead.go              Seal / Open (AES-128-GCM)
+//   internal/handshake/aead.go              Seal / Open (AES-GCM)
 //   internal/handshake/header_protector.go  aesHeaderProtector
 // (quic-go v0.52.0-beta.1, go.mod:7; reached from the reference through
 // quic.go:47-102; not in the reference tree).  The algorithms are FIPS-197
-// (AES-128), NIST SP 800-38D (GCM with a 96-bit nonce: J0 = nonce || 1,
-// payload counters from 2) and RFC 9001 sections 5.3 / 5.4.3 (nonce, AES
-// header protection: mask = AES-ECB(hp, sample)).  The CPU checker is
-// oracle/oracle.c (or_quic_seal2 / or_quic_open2), pinned by FIPS-197, the GCM
-// specification's test cases, RFC 9001 A.3 and OpenSSL
-// (tests/golden/quic_gcm.json).
+// (AES-128, AES-256), NIST SP 800-38D (GCM with a 96-bit nonce: J0 = nonce
+// || 1, payload counters from 2) and RFC 9001 sections 5.3 / 5.4.3 (nonce,
+// AES header protection: mask = AES-ECB(hp, sample)).  The CPU checker of
+// AES-128-GCM is oracle/oracle.c (or_quic_seal2 / or_quic_open2), pinned by
+// FIPS-197, the GCM specification's test cases, RFC 9001 A.3 and OpenSSL
+// (tests/golden/quic_gcm.json); AES-256-GCM is checked against OpenSSL-built
+// packets (tests/golden/quic_gcm256.json).  The two suites share every
+// kernel: the round count NR (10 or 14) is a template parameter, the key
+// schedules hold NR + 1 round keys, and GHASH does not depend on the key
+// size at all.
 //
 // gfx950 has no carry-less multiply and no AES instructions, so both run as
 // LDS table lookups, laid out for the LDS banking rules:
@@ -59,17 +64,30 @@
 
 namespace sq {
 
-constexpr uint32_t kGBlock = 768;  // 12 waves: one block per CU (156 KB of LDS)
+constexpr uint32_t kGBlock = 768;  // 12 waves: one block per CU (142-158.5 KiB of LDS)
 constexpr uint32_t kGWaves = kGBlock / kWave;
 // Packets per wave (owner lanes).  32 with 12-wave workgroups (the LDS
-// tables plus 32 records per wave fill 156 KB, 3 waves per SIMD) measured
+// tables plus 32 records per wave fill up to 158.5 KiB of the CU's 160: see
+// kLdsWords; 3 waves per SIMD) measured
 // seal 3,246 -> 3,146 us and open 3,252 -> 3,056 us against 16 packets in
 // 16-wave groups (4 waves per SIMD), three interleaved passes.
 constexpr uint32_t kGPpw = 32;
 static_assert(kGPpw <= 32, "chunk-list entries hold the packet in 5 bits (gcm_unit)");
 constexpr uint32_t kGCoopMax = 16 * kGcmPow;   // 2048 B
+// NR, everywhere below: the AES round count, 10 (AES-128) or 14 (AES-256), a
+// compile-time parameter so that every round loop stays fully unrolled.
+// The staged key's words in LDS (the staged kernel's tK), laid out as the
+// head of a keyring entry of that key size: the slots of the two key
+// schedules of NR + 1 round keys each, then the IV (3 words, padded to 4).
+// Only the IV is staged: the schedule slots (352 B, 480 B for NR 14) stay
+// unused, the round keys being read from the entry by scalar loads.
+template <int NR>
+constexpr uint32_t kTkIv = 2 * 4 * (NR + 1);
+template <int NR>
+constexpr uint32_t kTkWords = kTkIv<NR> + 4;
+static_assert(4 * (14 + 1) <= kGcmRkWords, "QuicGcmKeyDev / QGParams hold an AES-256 schedule");
 
-// ---------------------------------------------------------------- AES-128
+// ---------------------------------------------------------------- AES
 
 __device__ __forceinline__ uint32_t rotl(uint32_t x, int n) {
   return __builtin_amdgcn_alignbit(x, x, 32 - n);
@@ -133,10 +151,10 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 // T1[s_c+3.b3]) ^ rk (T2 = rotl16 T0, T3 = rotl16 T1; ShiftRows folded into
 // the byte picks), computed as xor3(a0, a1, rotl16(xor3(a2, a3, rotr16 rk)))
 // -- 3 VALU ops per column besides the 4 v_perm addresses; the key schedule
-// holds rounds 1-9 already rotated (sq_api.hip gcm_key).  The last round
-// takes the S-box byte (T0 byte 1, T1 bytes 2 and 3) instead.
+// holds rounds 1..NR-1 already rotated (sq_api.hip gcm_key).  The last
+// round, NR, takes the S-box byte (T0 byte 1, T1 bytes 2 and 3) instead.
 // R0 > 1: s holds the state entering round R0 (aes_ctr_n).
-template <int KM, int NB, int R0 = 1>
+template <int KM, int NR, int NB, int R0 = 1>
 __device__ __forceinline__ void aes_encrypt_n(const uint32_t *rk, const uint32_t *tT, uint32_t lo,
                                               uint32_t (&s)[NB][4]) {
   uint32_t k[4];
@@ -148,7 +166,7 @@ __device__ __forceinline__ void aes_encrypt_n(const uint32_t *rk, const uint32_t
       for (int c = 0; c < 4; c++) s[q][c] ^= k[c];
   }
 #pragma unroll
-  for (int r = R0; r < 10; r++) {
+  for (int r = R0; r < NR; r++) {
     uint32_t kr[4];  // (rotated by 16 in the key schedule)
     round_key<KM>(rk, r, kr);
     uint32_t t[NB][4];
@@ -167,7 +185,7 @@ __device__ __forceinline__ void aes_encrypt_n(const uint32_t *rk, const uint32_t
 #pragma unroll
       for (int c = 0; c < 4; c++) s[q][c] = t[q][c];
   }
-  round_key<KM>(rk, 10, k);
+  round_key<KM>(rk, NR, k);
   uint32_t t[NB][4];
 #pragma unroll
   for (int q = 0; q < NB; q++)
@@ -194,7 +212,8 @@ __device__ __forceinline__ void aes_encrypt_n(const uint32_t *rk, const uint32_t
 // 0's bytes, one into each column): the rest of both rounds is the same for
 // every block of a packet.  aes_ctr_pre computes those parts once per chunk
 // (27 lookups); aes_ctr_n then runs a block's rounds 1 and 2 in 5 lookups and
-// 12 VALU instead of 32 and ~60, and rounds 3-10 as aes_encrypt_n.
+// 12 VALU instead of 32 and ~60, and rounds 3..NR as aes_encrypt_n (rounds 1
+// and 2 read round keys 0-2 only: the precomputation is the same for NR 14).
 struct CtrPre {
   uint32_t c0;     // round-1 column 0 without the counter byte's term
   uint32_t f[4];   // round-2 columns without column 0's terms
@@ -232,7 +251,7 @@ __device__ __forceinline__ void aes_ctr_pre(const uint32_t *rk, const uint32_t *
   }
 }
 // keystream blocks for counters ctr[q] (< 256) under P's nonce and key
-template <int KM, int NB>
+template <int KM, int NR, int NB>
 __device__ __forceinline__ void aes_ctr_n(const uint32_t *rk, const uint32_t *tT, uint32_t lo,
                                           const CtrPre &P, const uint32_t (&ctr)[NB],
                                           uint32_t (&s)[NB][4]) {
@@ -247,14 +266,14 @@ __device__ __forceinline__ void aes_ctr_n(const uint32_t *rk, const uint32_t *tT
     s[q][2] = P.f[2] ^ rotl(t0at(tT, trow(col0, lo, 2)), 16);
     s[q][3] = P.f[3] ^ t1at(tT, trow(col0, lo, 1));
   }
-  aes_encrypt_n<KM, NB, 3>(rk, tT, lo, s);
+  aes_encrypt_n<KM, NR, NB, 3>(rk, tT, lo, s);
 }
 
-template <int KM>
+template <int KM, int NR>
 __device__ __forceinline__ void aes_encrypt(const uint32_t *rk, const uint32_t *tT, uint32_t lo,
                                             uint32_t (&s)[4]) {
   uint32_t b[1][4] = {{s[0], s[1], s[2], s[3]}};
-  aes_encrypt_n<KM, 1>(rk, tT, lo, b);
+  aes_encrypt_n<KM, NR, 1>(rk, tT, lo, b);
 #pragma unroll
   for (int c = 0; c < 4; c++) s[c] = b[0][c];
 }
@@ -412,7 +431,7 @@ __device__ __forceinline__ void ghash_absorb(uint32_t (&y)[4], const uint32_t (&
 
 // Key material of one packet: round keys, header-protection round keys,
 // IV, and the GHASH tables (table k-1 = H^k).
-template <int KM>
+template <int KM, int NR>
 struct GKey {
   const uint32_t *rk, *hrk, *iv, *hpos, *htab;
   // x <- x * H^(4 k) (k = 1 .. kGcmPow4)
@@ -438,8 +457,8 @@ struct GKey {
 // (zero past nv).  OB (fused Salamander layer): output (seal) or input
 // (open) bytes are also XORed with the packet's Salamander key; okr = the
 // key rotated to the first byte at src / dst (block j uses half j & 1).
-template <bool OPEN, int KM, bool OB>
-__device__ __forceinline__ void gcm_run(const GKey<KM> &K, const uint32_t *tT, uint32_t tcol,
+template <bool OPEN, int KM, bool OB, int NR>
+__device__ __forceinline__ void gcm_run(const GKey<KM, NR> &K, const uint32_t *tT, uint32_t tcol,
                                         const uint32_t (&nonce)[3], uint32_t ctr0, uint64_t src,
                                         uint64_t dst, uint32_t nv, uint32_t (&y)[4],
                                         uint32_t (&first32)[8], const uint32_t (&okr)[8]) {
@@ -470,7 +489,7 @@ __device__ __forceinline__ void gcm_run(const GKey<KM> &K, const uint32_t *tT, u
     load_blk(j + 3, nx[1]);
     uint32_t s2[2][4] = {{nonce[0], nonce[1], nonce[2], __builtin_bswap32(ctr0 + j)},
                          {nonce[0], nonce[1], nonce[2], __builtin_bswap32(ctr0 + j + 1)}};
-    aes_encrypt_n<KM, 2>(K.rk, tT, tcol, s2);
+    aes_encrypt_n<KM, NR, 2>(K.rk, tT, tcol, s2);
 #pragma unroll
     for (int q = 0; q < 2; q++) {
       if (q == 1 && j + 1 >= nchunk) break;
@@ -520,8 +539,8 @@ __device__ __forceinline__ void gcm_run(const GKey<KM> &K, const uint32_t *tT, u
 // ct32 (seal): the packet's LDS words that receive ciphertext blocks 0 and 1
 // (the first chunk may be short: block 1 can be the second chunk's).
 // OB: as gcm_run (okr = the key rotated to the payload start).
-template <bool OPEN, int KM, bool OB>
-__device__ __forceinline__ void gcm_chunk(const GKey<KM> &K, const uint32_t *tT, uint32_t tcol,
+template <bool OPEN, int KM, bool OB, int NR>
+__device__ __forceinline__ void gcm_chunk(const GKey<KM, NR> &K, const uint32_t *tT, uint32_t tcol,
                                           const uint32_t (&nonce)[3], uint32_t blk0,
                                           uint32_t nfull, uint64_t src, uint64_t dst,
                                           const uint32_t (&y0)[4], uint32_t (&y)[4],
@@ -548,7 +567,7 @@ __device__ __forceinline__ void gcm_chunk(const GKey<KM> &K, const uint32_t *tT,
   for (int h = 0; h < 4; h += 2) {
     uint32_t s2[2][4];
     const uint32_t cq[2] = {ctr + h, ctr + h + 1};
-    aes_ctr_n<KM, 2>(K.rk, tT, tcol, P, cq, s2);
+    aes_ctr_n<KM, NR, 2>(K.rk, tT, tcol, P, cq, s2);
 #pragma unroll
     for (int q = 0; q < 2; q++) {
       const int s = h + q;
@@ -583,12 +602,12 @@ __device__ __forceinline__ void gcm_chunk(const GKey<KM> &K, const uint32_t *tT,
 }
 
 // 5 header-protection mask bytes (RFC 9001 5.4.3): AES-ECB(hp, sample)
-template <int KM>
-__device__ __forceinline__ void gcm_hp_mask(const GKey<KM> &K, const uint32_t *tT, uint32_t tcol,
+template <int KM, int NR>
+__device__ __forceinline__ void gcm_hp_mask(const GKey<KM, NR> &K, const uint32_t *tT, uint32_t tcol,
                                             const uint32_t (&sample)[4], uint32_t &m0,
                                             uint32_t &m1) {
   uint32_t s[4] = {sample[0], sample[1], sample[2], sample[3]};
-  aes_encrypt<KM>(K.hrk, tT, tcol, s);
+  aes_encrypt<KM, NR>(K.hrk, tT, tcol, s);
   m0 = s[0];
   m1 = s[1] & 0xFFu;
 }
@@ -607,16 +626,16 @@ struct alignas(16) GRec {
 };
 
 // STAGED: the workgroup's staged key (round keys, IV and GHASH tables in LDS)
-template <bool MULTI, bool STAGED>
-__device__ __forceinline__ GKey<MULTI ? 1 : (STAGED ? 2 : 0)> key_of(
+template <bool MULTI, bool STAGED, int NR>
+__device__ __forceinline__ GKey<MULTI ? 1 : (STAGED ? 2 : 0), NR> key_of(
     const QGParams &Q, uint32_t kid, const uint32_t *tP, const uint32_t *tH, const uint32_t *tK) {
-  GKey<MULTI ? 1 : (STAGED ? 2 : 0)> K;
+  GKey<MULTI ? 1 : (STAGED ? 2 : 0), NR> K;
   if (MULTI) {
     const QuicGcmKeyDev *E = Q.keys + kid;
     K.rk = E->rk; K.hrk = E->hrk; K.iv = E->iv;
     K.hpos = &E->hpos[0][0][0]; K.htab = &E->htab[0][0][0];
   } else if (STAGED) {  // kid: the staged key
-    K.rk = Q.keys[kid].rk; K.hrk = Q.keys[kid].hrk; K.iv = tK + 88;
+    K.rk = Q.keys[kid].rk; K.hrk = Q.keys[kid].hrk; K.iv = tK + kTkIv<NR>;
     K.hpos = tP; K.htab = tH;
   } else {
     K.rk = Q.rk0; K.hrk = Q.hrk0;  // (kernarg: scalar loads)
@@ -629,11 +648,18 @@ constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 
 // Copy keyring entry E's IV and GHASH tables into the block's LDS (every
 // thread of the block takes part).
+template <int NR>
 __device__ __forceinline__ void stage_key(const QuicGcmKeyDev *E, uint32_t *tP, uint32_t *tH,
                                           uint32_t *tK) {
-  if (threadIdx.x < 3) tK[88 + threadIdx.x] = E->iv[threadIdx.x];  // (round keys: scalar loads)
+  // (round keys: scalar loads.)  The thread index goes through an empty asm,
+  // so the addresses below are computed here, at each staging, instead of
+  // once before the step loop: held in VGPRs through every unit they were
+  // what spilled (the kernels sit at the 168-VGPR ceiling of 3 waves per SIMD)
+  uint32_t t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  if (t < 3) tK[kTkIv<NR> + t] = E->iv[t];
   const uint32_t *src = &E->hpos[0][0][0];  // hpos then htab, contiguous
-  for (uint32_t i = threadIdx.x; i < (32 + kGcmPow4) * 16; i += kGBlock) {
+  for (uint32_t i = t; i < (32 + kGcmPow4) * 16; i += kGBlock) {
     const u32x4 v = gld<u32x4>((uint64_t)(src + 4 * i));
     if (i < 32 * 16) *(u32x4 *)(tP + 4 * i) = v;
     else *(u32x4 *)(tH + 4 * (i - 32 * 16)) = v;
@@ -643,7 +669,7 @@ __device__ __forceinline__ void stage_key(const QuicGcmKeyDev *E, uint32_t *tP, 
 // One unit (up to kGPpw packets) of a wave: the three phases.  recs = the
 // wave's records.  STAGED (with MULTI false): every packet of the unit uses
 // the workgroup's staged key.
-template <bool OPEN, bool MULTI, bool OB, bool STAGED>
+template <bool OPEN, bool MULTI, bool OB, bool STAGED, int NR>
 __device__ __forceinline__ void gcm_unit(const QGParams &Q, uint64_t base, uint32_t cnt,
                                          uint32_t skid, uint32_t lane,
                                          const uint32_t *tT, uint32_t tcol, const uint32_t *tP,
@@ -676,7 +702,7 @@ __device__ __forceinline__ void gcm_unit(const QGParams &Q, uint64_t base, uint3
       if (OPEN && Q.pn_out) Q.pn_out[p] = 0;  // rejected: pn_out 0 (as below)
     }
   }
-  const GKey<KM> K = key_of<MULTI, STAGED>(Q, kid, tP, tH, tK);
+  const GKey<KM, NR> K = key_of<MULTI, STAGED, NR>(Q, kid, tP, tH, tK);
   if (live) {
     src = (uint64_t)Q.in + Q.in_off[p];
     dst = (uint64_t)Q.out + Q.out_off[p];
@@ -739,7 +765,7 @@ __device__ __forceinline__ void gcm_unit(const QGParams &Q, uint64_t base, uint3
 #pragma unroll
         for (int w = 0; w < 4; w++) hd[4 + w] ^= k4[w];
       }
-      gcm_hp_mask<KM>(K, tT, tcol, sample, m0, m1);
+      gcm_hp_mask(K, tT, tcol, sample, m0, m1);
       const uint32_t pfirst = hd[0] & 0xFFu;
       first = pfirst ^ (m0 & ((pfirst & 0x80) ? 0x0Fu : 0x1Fu));
       pn_len = (first & 3) + 1;
@@ -852,7 +878,7 @@ __device__ __forceinline__ void gcm_unit(const QGParams &Q, uint64_t base, uint3
       // must never run after the one behind it)
       const uint32_t e = clist[T - 1 - f], k = e >> 5;
       GRec &R = recs[e & 31u];
-      const GKey<KM> KB = key_of<MULTI, STAGED>(Q, R.kid, tP, tH, tK);
+      const GKey<KM, NR> KB = key_of<MULTI, STAGED, NR>(Q, R.kid, tP, tH, tK);
       // chunk k from the end: full blocks [end - nfull, end), end = npf - 4 k
       const uint32_t npf = R.pl / 16, b = (npf + 3) / 4 - 1 - k;
       const uint32_t end = npf - 4 * k, nfull = end < 4 ? end : 4u;
@@ -890,7 +916,7 @@ __device__ __forceinline__ void gcm_unit(const QGParams &Q, uint64_t base, uint3
       const uint64_t ps = src + hdr + 16ull * k;
       uint32_t x[4], c[4], ks[4] = {nonce[0], nonce[1], nonce[2], __builtin_bswap32(2u + k)};
       load16(ps, src + hdr + pl, x);
-      aes_encrypt<KM>(K.rk, tT, tcol, ks);
+      aes_encrypt<KM, NR>(K.rk, tT, tcol, ks);
       uint32_t kw[4];
 #pragma unroll
       for (int w = 0; w < 4; w++) {
@@ -925,7 +951,7 @@ __device__ __forceinline__ void gcm_unit(const QGParams &Q, uint64_t base, uint3
   y[3] ^= 8 * pl;
   gmul_pos<MULTI>(y, K.hpos);
   uint32_t tag[4] = {nonce[0], nonce[1], nonce[2], __builtin_bswap32(1u)};
-  aes_encrypt<KM>(K.rk, tT, tcol, tag);  // E(K, J0)
+  aes_encrypt<KM, NR>(K.rk, tT, tcol, tag);  // E(K, J0)
 #pragma unroll
   for (int w = 0; w < 4; w++) tag[w] ^= __builtin_bswap32(y[w]);
   if (OPEN) {
@@ -961,7 +987,7 @@ __device__ __forceinline__ void gcm_unit(const QGParams &Q, uint64_t base, uint3
     }
   }
   uint32_t m0, m1;
-  gcm_hp_mask<KM>(K, tT, tcol, sample, m0, m1);
+  gcm_hp_mask(K, tT, tcol, sample, m0, m1);
   const uint32_t kb0 = OB ? okey[0] & 0xFFu : 0u;
   gst<uint8_t>(dst, (uint8_t)(first ^ kb0 ^ (m0 & ((first & 0x80) ? 0x0Fu : 0x1Fu))));
   for (uint32_t i = 0; i < pn_len; i++) {
@@ -984,6 +1010,13 @@ template <bool TABLES, uint32_t TK>
 constexpr uint32_t kLdsWords = (TABLES ? 32 * 64 + kGcmPow4 * 64 : 0u) + 256 * 64 +
                                (TK + 3) / 4 * 4 + (uint32_t)sizeof(GRec) * kGWaves * kGPpw / 4 +
                                kGWaves * kGList / 2;
+// Every image the kernels below instantiate fits gfx950's 160 KiB of LDS per
+// workgroup: 145,424 B (per-packet keys), 161,808 B (one key), and the
+// staged kernel's 162,160 B (AES-128) and 162,288 B (AES-256).
+static_assert(kLdsWords<false, 4> * 4 <= 160 * 1024 && kLdsWords<true, 4> * 4 <= 160 * 1024 &&
+                  kLdsWords<true, kTkWords<10>> * 4 <= 160 * 1024 &&
+                  kLdsWords<true, kTkWords<14>> * 4 <= 160 * 1024,
+              "the LDS image exceeds gfx950's 160 KiB per workgroup");
 template <bool TABLES, uint32_t TK>
 __device__ __forceinline__ void gcm_lds(uint32_t *lds, uint32_t *&tP, uint32_t *&tT, uint32_t *&tH,
                                         uint32_t *&tK, GRec (*&recs)[kGPpw],
@@ -1018,7 +1051,7 @@ __device__ __forceinline__ void stage_common(const QGParams &Q, uint32_t *tT, ui
 
 // One key (MULTI false) or per-packet keys from the keyring in global memory
 // (MULTI true, batches that are not grouped).
-template <bool OPEN, bool MULTI, bool OB>
+template <bool OPEN, bool MULTI, bool OB, int NR>
 __global__ __launch_bounds__(kGBlock) void quic_gcm_kernel(const QGParams Q) {
   // one LDS image laid out by hand (gcm_lds): the GHASH position tables at
   // address 0, so a lookup's position is its immediate offset (< 64 KiB)
@@ -1036,8 +1069,8 @@ __global__ __launch_bounds__(kGBlock) void quic_gcm_kernel(const QGParams Q) {
   for (uint64_t u = (uint64_t)blockIdx.x * kGWaves + wv; u < units; u += stride) {
     const uint64_t base = u * kGPpw;
     const uint32_t cnt = Q.n - base < kGPpw ? (uint32_t)(Q.n - base) : kGPpw;
-    gcm_unit<OPEN, MULTI, OB, false>(Q, base, cnt, 0u, lane, tT, tcol, tP, tH, tK, recs[wv],
-                                     clists[wv]);
+    gcm_unit<OPEN, MULTI, OB, false, NR>(Q, base, cnt, 0u, lane, tT, tcol, tP, tH, tK, recs[wv],
+                                         clists[wv]);
   }
 }
 
@@ -1052,13 +1085,13 @@ __global__ __launch_bounds__(kGBlock) void quic_gcm_kernel(const QGParams Q) {
 // units deferred to a per-packet launch, ran that launch's one unit-time,
 // 350-390 us, serially after the rest; each workgroup walking a contiguous
 // range of units measured slower than striding.)
-template <bool OPEN, bool OB>
+template <bool OPEN, bool OB, int NR>
 __global__ __launch_bounds__(kGBlock) void quic_gcm_staged_kernel(const QGParams Q) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords<true, 92>];
-  uint32_t *tP, *tT, *tH, *tK;  // tK[88..90]: the staged key's IV
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords<true, kTkWords<NR>>];
+  uint32_t *tP, *tT, *tH, *tK;  // tK[kTkIv<NR> ..]: the staged key's IV
   GRec(*recs)[kGPpw];
   uint16_t(*clists)[kGList];
-  gcm_lds<true, 92>(lds, tP, tT, tH, tK, recs, clists);
+  gcm_lds<true, kTkWords<NR>>(lds, tP, tT, tH, tK, recs, clists);
   stage_common<true>(Q, tT, tP, tH, tK);
   __syncthreads();
   const uint32_t lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
@@ -1081,7 +1114,7 @@ __global__ __launch_bounds__(kGBlock) void quic_gcm_staged_kernel(const QGParams
     const uint32_t k = lo;
     if (k != staged) {  // (block-uniform)
       __syncthreads();  // every wave is done with the previous key
-      stage_key(Q.keys + k, tP, tH, tK);
+      stage_key<NR>(Q.keys + k, tP, tH, tK);
       __syncthreads();
       staged = k;
     }
@@ -1090,8 +1123,8 @@ __global__ __launch_bounds__(kGBlock) void quic_gcm_staged_kernel(const QGParams
     const uint64_t first = ((uint64_t)j * kGWaves + wv) * kGPpw;  // within the key
     if (first >= cnt_k) continue;
     const uint32_t cnt = cnt_k - first < kGPpw ? (uint32_t)(cnt_k - first) : kGPpw;
-    gcm_unit<OPEN, false, OB, true>(Q, (uint64_t)rfl32(kstart[k]) + first, cnt, k,
-                                    lane, tT, tcol, tP, tH, tK, recs[wv], clists[wv]);
+    gcm_unit<OPEN, false, OB, true, NR>(Q, (uint64_t)rfl32(kstart[k]) + first, cnt, k,
+                                        lane, tT, tcol, tP, tH, tK, recs[wv], clists[wv]);
   }
 }
 
@@ -1259,23 +1292,42 @@ static uint64_t resident_blocks(const void *fn) {
   return (uint64_t)(per_cu < 1 ? 1 : per_cu) * (uint64_t)(cus < 1 ? 1 : cus);
 }
 
-template <bool OPEN, bool MULTI, bool OB>
+template <bool OPEN, bool MULTI, bool OB, int NR>
 static int launch_gcm(const QGParams *qp, hipStream_t s) {
-  // queried once (thread-safe static init)
-  static const uint64_t cap = resident_blocks((const void *)quic_gcm_kernel<OPEN, MULTI, OB>);
+  // queried once per instantiation (thread-safe static init)
+  static const uint64_t cap =
+      resident_blocks((const void *)quic_gcm_kernel<OPEN, MULTI, OB, NR>);
   static const uint64_t cap_st =
-      resident_blocks((const void *)quic_gcm_staged_kernel<OPEN, OB>);
+      resident_blocks((const void *)quic_gcm_staged_kernel<OPEN, OB, NR>);
   const uint64_t waves = ((uint64_t)qp->n + kGPpw - 1) / kGPpw;
   const uint64_t want = (waves + kGWaves - 1) / kGWaves;
   (void)hipGetLastError();  // (a stale error is not this launch's: sq_kernels.hip launch_k)
   if (MULTI && qp->perm) {  // grouped: every valid packet is in a step
-    hipLaunchKernelGGL((quic_gcm_staged_kernel<OPEN, OB>), dim3((uint32_t)(want < cap_st ? want : cap_st)),
-                       dim3(kGBlock), 0, s, *qp);
+    hipLaunchKernelGGL((quic_gcm_staged_kernel<OPEN, OB, NR>),
+                       dim3((uint32_t)(want < cap_st ? want : cap_st)), dim3(kGBlock), 0, s, *qp);
     return hipGetLastError() == hipSuccess ? 0 : -3;
   }
-  hipLaunchKernelGGL((quic_gcm_kernel<OPEN, MULTI, OB>), dim3((uint32_t)(want < cap ? want : cap)),
-                     dim3(kGBlock), 0, s, *qp);
+  hipLaunchKernelGGL((quic_gcm_kernel<OPEN, MULTI, OB, NR>),
+                     dim3((uint32_t)(want < cap ? want : cap)), dim3(kGBlock), 0, s, *qp);
   return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// the 8 kernel variants of one round count
+template <int NR>
+static int launch_gcm_nr(int open, const QGParams *qp, hipStream_t s) {
+  const bool multi = qp->key_id != nullptr;
+  if (qp->obfs) {
+    if (open)
+      return multi ? launch_gcm<true, true, true, NR>(qp, s)
+                   : launch_gcm<true, false, true, NR>(qp, s);
+    return multi ? launch_gcm<false, true, true, NR>(qp, s)
+                 : launch_gcm<false, false, true, NR>(qp, s);
+  }
+  if (open)
+    return multi ? launch_gcm<true, true, false, NR>(qp, s)
+                 : launch_gcm<true, false, false, NR>(qp, s);
+  return multi ? launch_gcm<false, true, false, NR>(qp, s)
+               : launch_gcm<false, false, false, NR>(qp, s);
 }
 
 }  // namespace sq
@@ -1284,11 +1336,7 @@ extern "C" int sq_launch_quic_gcm(int open, const sq::QGParams *qp, void *stream
   using namespace sq;
   if (qp->n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const bool multi = qp->key_id != nullptr;
-  if (qp->obfs) {
-    if (open) return multi ? launch_gcm<true, true, true>(qp, s) : launch_gcm<true, false, true>(qp, s);
-    return multi ? launch_gcm<false, true, true>(qp, s) : launch_gcm<false, false, true>(qp, s);
-  }
-  if (open) return multi ? launch_gcm<true, true, false>(qp, s) : launch_gcm<true, false, false>(qp, s);
-  return multi ? launch_gcm<false, true, false>(qp, s) : launch_gcm<false, false, false>(qp, s);
+  if (qp->nr == 10) return launch_gcm_nr<10>(open, qp, s);  // AES-128-GCM
+  if (qp->nr == 14) return launch_gcm_nr<14>(open, qp, s);  // AES-256-GCM
+  return -1;  // SQ_EINVAL: no kernel for this round count
 }

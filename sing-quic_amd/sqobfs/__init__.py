@@ -93,7 +93,7 @@ class QuicKey(ctypes.Structure):
 
     @classmethod
     def of(cls, key: bytes, iv: bytes, hp: bytes) -> "QuicKey":
-        """key / hp: 32 bytes (ChaCha20-Poly1305) or 16 (AES-128-GCM)."""
+        """key / hp: 32 bytes (ChaCha20-Poly1305, AES-256-GCM) or 16 (AES-128-GCM)."""
         assert len(key) in (16, 32) and len(hp) == len(key) and len(iv) == 12
         k = cls()
         ctypes.memmove(k.key, key, len(key))
@@ -111,7 +111,7 @@ class QuicBatch(ctypes.Structure):
 
 
 QUIC_EKEY, QUIC_ESHORT, QUIC_EAUTH = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD
-QUIC_CHACHA20_POLY1305, QUIC_AES_128_GCM = 0, 1  # SQOBFS_QUIC_* suites
+QUIC_CHACHA20_POLY1305, QUIC_AES_128_GCM, QUIC_AES_256_GCM = 0, 1, 2  # SQOBFS_QUIC_* suites
 
 
 class UdpView(ctypes.Structure):
@@ -803,7 +803,8 @@ class UdpConn:
 
 class QuicKeyring:
     """Device copy of per-connection QUIC 1-RTT keys (sqobfs_quic_keyring) of
-    one suite: QUIC_CHACHA20_POLY1305 (default) or QUIC_AES_128_GCM."""
+    one suite: QUIC_CHACHA20_POLY1305 (default), QUIC_AES_128_GCM or
+    QUIC_AES_256_GCM (32-byte key / hp)."""
 
     def __init__(self, ctx: Context, keys: list[QuicKey], suite: int = QUIC_CHACHA20_POLY1305):
         arr = (QuicKey * len(keys))(*keys)
