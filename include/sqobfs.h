@@ -371,6 +371,76 @@ int sqobfs_quic_seal(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
 int sqobfs_quic_open(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
                      const sqobfs_quic_batch *b, void *stream);
 
+/* ------------------------------------------------------------------------
+ * QUIC key update (RFC 9001 section 6): keys derived and rolled on the
+ * device from TLS traffic secrets, and the Key Phase of received packets.
+ * New symbols only: no struct above changes layout, so SQOBFS_ABI_VERSION
+ * stays as it is.
+ *
+ * quic-go (internal/handshake/updatable_aead.go) derives each generation's
+ * keys on the host and initiates an update after KeyUpdateInterval packets.
+ * Here a keyring made from secrets holds, for connection c, TWO entries:
+ * entry 2c + (g & 1) holds generation g, so a packet's Key Phase bit (0x04
+ * of a short header's first byte) is the low bit of its entry index.  After
+ * creation entry 2c holds generation 0 and entry 2c + 1 generation 1 (RFC
+ * 9001 6.1: the next keys are ready before they are needed).  The keyring
+ * keeps each connection's newest secret and generation number on the device.
+ * hp never changes: both entries of a connection carry the same one. */
+
+/* A TLS 1.3 traffic secret (client_/server_application_traffic_secret_N).
+ * The SHA-256 suites (ChaCha20-Poly1305, AES-128-GCM) use secret[0..32),
+ * TLS_AES_256_GCM_SHA384 all 48. */
+typedef struct sqobfs_quic_secret {
+  uint8_t secret[48];
+} sqobfs_quic_secret;
+
+/* A keyring of 2 * conns entries from one secret per connection (conns <=
+ * 32768: key ids are 16 bits): allocation, then a rekey of every connection
+ * with its secret.  For the GCM suites the key schedules and GHASH tables
+ * are built on the device. */
+int sqobfs_quic_keyring_create_secrets(sqobfs_ctx *ctx, uint32_t suite, uint32_t conns,
+                                       const sqobfs_quic_secret *secrets,
+                                       sqobfs_quic_keyring **out);
+
+/* Re-keys connections conn[0..n) of a keyring made from secrets.
+ *   secrets != NULL: slot conn[i] is reused for a new connection and starts
+ *     again at generations 0 and 1 from secrets[i]: key / iv / hp =
+ *     HKDF-Expand-Label(secret, "quic key" / "quic iv" / "quic hp", "",
+ *     key length / 12 / key length), the generation-1 secret =
+ *     HKDF-Expand-Label(secret, "quic ku", "", hash length) (RFC 9001 5.1,
+ *     6.1; SHA-384 for AES-256-GCM, SHA-256 otherwise).
+ *   secrets == NULL: a key update.  With g the connection's newest
+ *     generation, the entry holding g - 1 is overwritten with generation
+ *     g + 1, derived from the stored secret of g; the stored secret and
+ *     generation advance; the entry holding g is not touched.
+ * conn[] must be distinct and below conns, and the keyring made by
+ * sqobfs_quic_keyring_create_secrets: else SQ_EINVAL, before anything is
+ * launched.  The work is queued on `stream` (NULL: the context's stream) and
+ * the call returns when it has completed.  Ordering it after launches that
+ * still need the overwritten generation is the caller's job, as with any
+ * other write to memory a launch reads.  Not to be called concurrently with
+ * launches that use the keyring with key_id == NULL when connection 0 is
+ * among conn[] (the keyring's copy of entry 0 is refreshed). */
+int sqobfs_quic_keyring_rekey(sqobfs_ctx *ctx, sqobfs_quic_keyring *kr, uint32_t n,
+                              const uint32_t *conn, const sqobfs_quic_secret *secrets,
+                              void *stream);
+
+/* Which entry each received packet needs, before open: b is used as open
+ * uses it (in, in_off, in_len, pn_offset, key_id; the input is not
+ * modified).  For a short-header packet
+ *   key_id_out[i] = (key_id[i] & ~1) | Key Phase bit,
+ * the bit read under the header-protection mask of entry key_id[i] (entry 0
+ * when key_id is NULL).  key_id_out[i] = key_id[i] (or 0) for long headers
+ * (they have no key phase), packets too short to sample and out-of-range
+ * ids: open reports those exactly as before.  key_id_out (device, [n]) may
+ * then be passed as key_id of sqobfs_quic_open in the same stream.  Works
+ * for every keyring whose entry pairs share hp; for keyrings not made from
+ * secrets the pairing is the caller's convention.  Wire datagrams of the
+ * fused Salamander path are obfuscated: de-obfuscate them first and use
+ * sqobfs_quic_open, there is no fused resolver. */
+int sqobfs_quic_key_phase(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
+                          const sqobfs_quic_batch *b, uint16_t *key_id_out, void *stream);
+
 /* QUIC protection and the Salamander layer in ONE pass (Hysteria2's send and
  * receive path: quic-go seals a packet, then SalamanderPacketConn.WriteTo
  * obfuscates the datagram, salamander.go:57-70; ReadFrom then Open on the

@@ -8,6 +8,7 @@
 // path (sqobfs_cpu_run, host keyrings; host/sq_cpu.cpp), which the packet
 // conn engine picks for small batches and when there is no working GPU.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -158,6 +159,13 @@ struct sqobfs_quic_keyring {
   sq::QuicGcmKeyDev *gtable = nullptr;  // device (AES-128-GCM, AES-256-GCM)
   uint32_t *t0 = nullptr;               // device AES T-table (256 words)
   uint32_t grk0[sq::kGcmRkWords], ghrk0[sq::kGcmRkWords], giv0[3];
+  // made from secrets (sqobfs_quic_keyring_create_secrets): count = 2 conns,
+  // connection c's generation g in entry 2c + (g & 1); device state of the
+  // key roll (sq_quic_keys.hip), all NULL / 0 for a keyring made from keys
+  uint32_t conns = 0;
+  uint32_t *sec = nullptr;   // [conns][12] newest generation's secret
+  uint32_t *gen = nullptr;   // [conns] newest generation
+  uint32_t *hkey = nullptr;  // AES-GCM: [count][4] H of each entry
 };
 
 // sqobfs_shard_launch: one completion event per context of the step
@@ -1298,7 +1306,167 @@ void sqobfs_quic_keyring_destroy(sqobfs_quic_keyring *kr) {
   tab_free_async(kr->table, kr->ctx->rel);
   tab_free_async(kr->gtable, kr->ctx->rel);
   tab_free_async(kr->t0, kr->ctx->rel);
+  tab_free_async(kr->sec, kr->ctx->rel);
+  tab_free_async(kr->gen, kr->ctx->rel);
+  tab_free_async(kr->hkey, kr->ctx->rel);
   delete kr;
+}
+
+// conn[0..n) distinct and below conns (sqobfs_quic_keyring_rekey: two lanes
+// would otherwise roll one connection's state at once)
+static bool conns_distinct(const uint32_t *conn, uint32_t n, uint32_t conns) {
+  if (n > conns) return false;
+  std::vector<bool> seen(conns, false);
+  for (uint32_t i = 0; i < n; i++) {
+    if (conn[i] >= conns || seen[conn[i]]) return false;
+    seen[conn[i]] = true;
+  }
+  return true;
+}
+
+int sqobfs_quic_keyring_rekey(sqobfs_ctx *ctx, sqobfs_quic_keyring *kr, uint32_t n,
+                              const uint32_t *conn, const sqobfs_quic_secret *secrets,
+                              void *stream) {
+  if (!ctx || !kr || kr->ctx != ctx || !kr->sec) return SQ_EINVAL;
+  if (n == 0) return SQ_OK;
+  if (!conn || !conns_distinct(conn, n, kr->conns)) return SQ_EINVAL;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  hipStream_t s = pick_stream(ctx, stream);
+  // the launch's arguments: conn[n], then secrets[n] (16-byte aligned)
+  const size_t cbytes = ((size_t)n * sizeof(uint32_t) + 15) & ~(size_t)15;
+  const size_t bytes = cbytes + (secrets ? (size_t)n * sizeof(sqobfs_quic_secret) : 0);
+  uint8_t *args = nullptr;
+  hipError_t e = tab_alloc((void **)&args, bytes, s);
+  if (e != hipSuccess) return hip_status(e);
+  e = hipMemcpyAsync(args, conn, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && secrets)
+    e = hipMemcpyAsync(args + cbytes, secrets, (size_t)n * sizeof(sqobfs_quic_secret),
+                       hipMemcpyHostToDevice, s);
+  int st = hip_status(e);
+  if (st == SQ_OK) {
+    sq::QKeysParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.conn = (const uint32_t *)args;
+    kp.secrets = secrets ? args + cbytes : nullptr;
+    kp.sec = kr->sec;
+    kp.gen = kr->gen;
+    kp.keys = kr->table;
+    kp.gkeys = kr->gtable;
+    kp.hkey = kr->hkey;
+    kp.t0 = kr->t0;
+    kp.n = n;
+    kp.suite = kr->suite;
+    st = sq_launch_quic_rekey(&kp, s);
+  }
+  // entry 0 changed: refresh the copies that single-key launches pass in the
+  // kernarg segment
+  bool has0 = false;
+  for (uint32_t i = 0; i < n && !has0; i++) has0 = conn[i] == 0;
+  sq::QuicKeyDev h0;
+  struct { uint32_t rk[sq::kGcmRkWords], hrk[sq::kGcmRkWords], iv[3]; } g0;
+  static_assert(offsetof(sq::QuicGcmKeyDev, hrk) == sizeof g0.rk &&
+                    offsetof(sq::QuicGcmKeyDev, iv) == sizeof g0.rk + sizeof g0.hrk,
+                "head of QuicGcmKeyDev");
+  if (st == SQ_OK && has0)
+    st = hip_status(kr->table ? hipMemcpyAsync(&h0, kr->table, sizeof h0, hipMemcpyDeviceToHost, s)
+                              : hipMemcpyAsync(&g0, kr->gtable, sizeof g0,
+                                               hipMemcpyDeviceToHost, s));
+  tab_free_async(args, s);
+  const int sy = hip_status(hipStreamSynchronize(s));
+  if (st == SQ_OK) st = sy;
+  if (st == SQ_OK && has0) {
+    if (kr->table) {
+      kr->host0 = h0;
+    } else {
+      memcpy(kr->grk0, g0.rk, sizeof kr->grk0);
+      memcpy(kr->ghrk0, g0.hrk, sizeof kr->ghrk0);
+      memcpy(kr->giv0, g0.iv, sizeof kr->giv0);
+    }
+  }
+  return st;
+}
+
+int sqobfs_quic_keyring_create_secrets(sqobfs_ctx *ctx, uint32_t suite, uint32_t conns,
+                                       const sqobfs_quic_secret *secrets,
+                                       sqobfs_quic_keyring **out) {
+  if (out) *out = nullptr;
+  if (!ctx || !out || conns == 0 || conns > sq::kQuicMaxConns || !secrets) return SQ_EINVAL;
+  if (suite != SQOBFS_QUIC_CHACHA20_POLY1305 && suite != SQOBFS_QUIC_AES_128_GCM &&
+      suite != SQOBFS_QUIC_AES_256_GCM)
+    return SQ_EINVAL;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  sqobfs_quic_keyring *kr = new (std::nothrow) sqobfs_quic_keyring();
+  if (!kr) return SQ_ENOMEM;
+  kr->ctx = ctx;
+  kr->suite = suite;
+  kr->conns = conns;
+  kr->count = 2 * conns;
+  memset(&kr->host0, 0, sizeof kr->host0);
+  const bool gcm = suite != SQOBFS_QUIC_CHACHA20_POLY1305;
+  const size_t tbytes = (gcm ? sizeof(sq::QuicGcmKeyDev) : sizeof(sq::QuicKeyDev)) * kr->count;
+  hipStream_t s = ctx->stream;
+  // zeroed: the schedule words an AES-128 entry does not use and the pad
+  // words stay 0, as in a keyring made from keys
+  hipError_t e = tab_alloc(gcm ? (void **)&kr->gtable : (void **)&kr->table, tbytes, s);
+  if (e == hipSuccess) e = hipMemsetAsync(gcm ? (void *)kr->gtable : (void *)kr->table, 0, tbytes, s);
+  if (e == hipSuccess)
+    e = tab_alloc((void **)&kr->sec, sizeof(uint32_t) * sq::kQuicSecretWords * conns, s);
+  if (e == hipSuccess) e = tab_alloc((void **)&kr->gen, sizeof(uint32_t) * conns, s);
+  if (e == hipSuccess && gcm) {
+    e = tab_alloc((void **)&kr->hkey, sizeof(uint32_t) * 4 * kr->count, s);
+    if (e == hipSuccess) e = tab_alloc((void **)&kr->t0, sizeof(uint32_t) * 256, s);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(kr->t0, aes_tables().t0, sizeof(uint32_t) * 256, hipMemcpyHostToDevice, s);
+  }
+  int st = hip_status(e);
+  if (st == SQ_OK) {
+    std::vector<uint32_t> all(conns);
+    for (uint32_t c = 0; c < conns; c++) all[c] = c;
+    st = sqobfs_quic_keyring_rekey(ctx, kr, conns, all.data(), secrets, nullptr);
+  }
+  if (st != SQ_OK) {
+    (void)hipStreamSynchronize(s);
+    tab_free_async(kr->table, s);
+    tab_free_async(kr->gtable, s);
+    tab_free_async(kr->t0, s);
+    tab_free_async(kr->sec, s);
+    tab_free_async(kr->gen, s);
+    tab_free_async(kr->hkey, s);
+    (void)hipStreamSynchronize(s);
+    delete kr;
+    return st;
+  }
+  *out = kr;
+  return SQ_OK;
+}
+
+int sqobfs_quic_key_phase(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
+                          const sqobfs_quic_batch *b, uint16_t *key_id_out, void *stream) {
+  if (!ctx || !kr || kr->ctx != ctx || !b || b->flags || !key_id_out) return SQ_EINVAL;
+  if (b->n == 0) return SQ_OK;
+  if (!b->in || !b->in_off || !b->in_len || !b->pn_offset) return SQ_EINVAL;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  sq::QPhaseParams pp;
+  memset(&pp, 0, sizeof pp);
+  pp.in = b->in;
+  pp.in_off = b->in_off;
+  pp.in_len = b->in_len;
+  pp.pn_offset = b->pn_offset;
+  pp.key_id = b->key_id;
+  pp.key_id_out = key_id_out;
+  pp.keys = kr->table;
+  pp.gkeys = kr->gtable;
+  pp.t0 = kr->t0;
+  pp.n = b->n;
+  pp.n_keys = kr->count;
+  pp.suite = kr->suite;
+  hipStream_t s = pick_stream(ctx, stream);
+  const int st = sq_launch_quic_key_phase(&pp, s);
+  if (st == SQ_OK) kr->uses.note(s);
+  return st;
 }
 
 static int quic_launch(int open, sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,

@@ -1,4 +1,4 @@
-// sq_hash.h -- lane-parallel BLAKE2b / SHA-256 compression for gfx950.
+// sq_hash.h -- lane-parallel BLAKE2b / SHA-256 / SHA-512 compression for gfx950.
 //
 // Each lane of a wave compresses a DIFFERENT packet's psk||salt block, so the
 // 64 lanes run the same straight-line code with no cross-lane traffic.
@@ -184,6 +184,96 @@ __device__ __host__ inline void s2_init(uint32_t st[8]) {
   st[5] = 0x9b05688c;
   st[6] = 0x1f83d9ab;
   st[7] = 0x5be0cd19;
+}
+
+// ---------------------------------------------------------------- SHA-512
+//
+// FIPS 180-4 section 6.4 compression on 64-bit words (SHA-384 of the QUIC
+// key schedule, sq_quic_keys.hip).  Rotations are v_alignbit_b32 pairs as in
+// BLAKE2b; a rotation by 32 or more swaps the halves first.  The 80 rounds
+// run as 5 passes of 16 unrolled rounds with the round constants read from
+// constant memory (scalar loads): fully unrolled, the compiler keeps the 80
+// 64-bit constants in VGPR pairs across a caller's loop and spills.
+
+template <int N>
+__device__ __forceinline__ uint64_t s5_rotr(uint64_t x) {
+  if (N < 32) return b2_rotr_lt32<N>(x);
+  if (N == 32) return b2_rotr32(x);
+  return b2_rotr_lt32<(N > 32 ? N - 32 : 1)>(b2_rotr32(x));
+}
+
+__device__ __forceinline__ void s5_compress(uint64_t st[8], const uint64_t m[16]) {
+  static constexpr uint64_t K[80] = {
+      0x428a2f98d728ae22ULL, 0x7137449123ef65cdULL, 0xb5c0fbcfec4d3b2fULL, 0xe9b5dba58189dbbcULL,
+      0x3956c25bf348b538ULL, 0x59f111f1b605d019ULL, 0x923f82a4af194f9bULL, 0xab1c5ed5da6d8118ULL,
+      0xd807aa98a3030242ULL, 0x12835b0145706fbeULL, 0x243185be4ee4b28cULL, 0x550c7dc3d5ffb4e2ULL,
+      0x72be5d74f27b896fULL, 0x80deb1fe3b1696b1ULL, 0x9bdc06a725c71235ULL, 0xc19bf174cf692694ULL,
+      0xe49b69c19ef14ad2ULL, 0xefbe4786384f25e3ULL, 0x0fc19dc68b8cd5b5ULL, 0x240ca1cc77ac9c65ULL,
+      0x2de92c6f592b0275ULL, 0x4a7484aa6ea6e483ULL, 0x5cb0a9dcbd41fbd4ULL, 0x76f988da831153b5ULL,
+      0x983e5152ee66dfabULL, 0xa831c66d2db43210ULL, 0xb00327c898fb213fULL, 0xbf597fc7beef0ee4ULL,
+      0xc6e00bf33da88fc2ULL, 0xd5a79147930aa725ULL, 0x06ca6351e003826fULL, 0x142929670a0e6e70ULL,
+      0x27b70a8546d22ffcULL, 0x2e1b21385c26c926ULL, 0x4d2c6dfc5ac42aedULL, 0x53380d139d95b3dfULL,
+      0x650a73548baf63deULL, 0x766a0abb3c77b2a8ULL, 0x81c2c92e47edaee6ULL, 0x92722c851482353bULL,
+      0xa2bfe8a14cf10364ULL, 0xa81a664bbc423001ULL, 0xc24b8b70d0f89791ULL, 0xc76c51a30654be30ULL,
+      0xd192e819d6ef5218ULL, 0xd69906245565a910ULL, 0xf40e35855771202aULL, 0x106aa07032bbd1b8ULL,
+      0x19a4c116b8d2d0c8ULL, 0x1e376c085141ab53ULL, 0x2748774cdf8eeb99ULL, 0x34b0bcb5e19b48a8ULL,
+      0x391c0cb3c5c95a63ULL, 0x4ed8aa4ae3418acbULL, 0x5b9cca4f7763e373ULL, 0x682e6ff3d6b2b8a3ULL,
+      0x748f82ee5defb2fcULL, 0x78a5636f43172f60ULL, 0x84c87814a1f0ab72ULL, 0x8cc702081a6439ecULL,
+      0x90befffa23631e28ULL, 0xa4506cebde82bde9ULL, 0xbef9a3f7b2c67915ULL, 0xc67178f2e372532bULL,
+      0xca273eceea26619cULL, 0xd186b8c721c0c207ULL, 0xeada7dd6cde0eb1eULL, 0xf57d4f7fee6ed178ULL,
+      0x06f067aa72176fbaULL, 0x0a637dc5a2c898a6ULL, 0x113f9804bef90daeULL, 0x1b710b35131c471bULL,
+      0x28db77f523047d84ULL, 0x32caab7b40c72493ULL, 0x3c9ebe0a15c9bebcULL, 0x431d67c49c100d4cULL,
+      0x4cc5d4becb3e42b6ULL, 0x597f299cfc657e2aULL, 0x5fcb6fab3ad6faecULL, 0x6c44198c4a475817ULL};
+  uint64_t w[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) w[i] = m[i];
+  uint64_t a = st[0], b = st[1], c = st[2], d = st[3];
+  uint64_t e = st[4], f = st[5], g = st[6], h = st[7];
+#pragma unroll 1
+  for (int r = 0; r < 80; r += 16) {
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const uint64_t S1 = s5_rotr<14>(e) ^ s5_rotr<18>(e) ^ s5_rotr<41>(e);
+      const uint64_t ch = (e & f) ^ (~e & g);
+      const uint64_t t1 = h + S1 + ch + K[r + j] + w[j];
+      const uint64_t S0 = s5_rotr<28>(a) ^ s5_rotr<34>(a) ^ s5_rotr<39>(a);
+      const uint64_t mj = (a & b) ^ (a & c) ^ (b & c);
+      h = g;
+      g = f;
+      f = e;
+      e = d + t1;
+      d = c;
+      c = b;
+      b = a;
+      a = t1 + S0 + mj;
+      // the word of 16 rounds on: W[i + 16] = W[i] + s0(W[i + 1]) + W[i + 9]
+      // + s1(W[i + 14]) (computed, unused, in the last pass)
+      const uint64_t x1 = w[(j + 1) & 15], x14 = w[(j + 14) & 15];
+      const uint64_t s0 = s5_rotr<1>(x1) ^ s5_rotr<8>(x1) ^ (x1 >> 7);
+      const uint64_t s1 = s5_rotr<19>(x14) ^ s5_rotr<61>(x14) ^ (x14 >> 6);
+      w[j] = w[j] + s0 + w[(j + 9) & 15] + s1;
+    }
+  }
+  st[0] += a;
+  st[1] += b;
+  st[2] += c;
+  st[3] += d;
+  st[4] += e;
+  st[5] += f;
+  st[6] += g;
+  st[7] += h;
+}
+
+// SHA-384 initial hash value (FIPS 180-4 section 5.3.4)
+__device__ __host__ inline void s5_init384(uint64_t st[8]) {
+  st[0] = 0xcbbb9d5dc1059ed8ULL;
+  st[1] = 0x629a292a367cd507ULL;
+  st[2] = 0x9159015a3070dd17ULL;
+  st[3] = 0x152fecd8f70e5939ULL;
+  st[4] = 0x67332667ffc00b31ULL;
+  st[5] = 0x8eb44a8768581511ULL;
+  st[6] = 0xdb0c2e0d64f98fa7ULL;
+  st[7] = 0x47b5481dbefa4fa4ULL;
 }
 
 // ---------------------------------------------------------------- ChaCha20

@@ -174,7 +174,48 @@ struct QGParams {
   PskEntry opsk;         // the Salamander keyring's entry 0
 };
 
+// QUIC key derivation and key roll (sq_quic_keys.hip): a keyring made from
+// TLS traffic secrets holds connection c's generation g in entry 2c + (g & 1)
+// and keeps, per connection, the newest generation's secret and its number.
+constexpr uint32_t kQuicSecretBytes = 48;               // sqobfs_quic_secret
+constexpr uint32_t kQuicSecretWords = kQuicSecretBytes / 4;
+constexpr uint32_t kQuicMaxConns = 32768;               // 2 entries each, 16-bit key ids
+struct QKeysParams {
+  const uint32_t *conn;    // [n] connections to (re)key, distinct (device)
+  const uint8_t *secrets;  // [n * 48] new connections' secrets (device), or
+                           // NULL: key update from the stored secrets
+  uint32_t *sec;           // [conns][12] newest secret, big-endian words
+  uint32_t *gen;           // [conns] newest generation
+  QuicKeyDev *keys;        // the keyring's table: ChaCha20-Poly1305 ...
+  QuicGcmKeyDev *gkeys;    // ... or AES-GCM
+  uint32_t *hkey;          // AES-GCM: [entries][4] H = E(K, 0) as big-endian
+                           // words, from the derivation to the table pass
+  const uint32_t *t0;      // AES T-table (256 words)
+  uint32_t n;
+  uint32_t suite;          // SQOBFS_QUIC_*
+};
+
+// Key-phase resolver launch (sq_quic_keys.hip): the batch as open reads it.
+struct QPhaseParams {
+  const uint8_t *in;
+  const uint64_t *in_off;
+  const uint32_t *in_len;
+  const uint16_t *pn_offset;
+  const uint16_t *key_id;
+  uint16_t *key_id_out;
+  const QuicKeyDev *keys;
+  const QuicGcmKeyDev *gkeys;
+  const uint32_t *t0;
+  uint32_t n;
+  uint32_t n_keys;
+  uint32_t suite;
+};
+
 }  // namespace sq
+
+// launchers implemented in sq_quic_keys.hip
+extern "C" int sq_launch_quic_rekey(const sq::QKeysParams *kp, void *stream);
+extern "C" int sq_launch_quic_key_phase(const sq::QPhaseParams *pp, void *stream);
 
 // host helpers implemented in sq_api.hip
 // poll a stream for up to `us` microseconds: 0 = drained, 1 = still busy, <0 error

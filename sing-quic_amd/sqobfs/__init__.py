@@ -102,6 +102,19 @@ class QuicKey(ctypes.Structure):
         return k
 
 
+class QuicSecret(ctypes.Structure):
+    """sqobfs_quic_secret: a TLS 1.3 traffic secret (32 bytes for the SHA-256
+    suites, 48 for TLS_AES_256_GCM_SHA384)."""
+    _fields_ = [("secret", ctypes.c_uint8 * 48)]
+
+    @classmethod
+    def of(cls, secret: bytes) -> "QuicSecret":
+        assert len(secret) in (32, 48)
+        s = cls()
+        ctypes.memmove(s.secret, secret, len(secret))
+        return s
+
+
 class QuicBatch(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("in_", ctypes.c_void_p),
                 ("in_off", ctypes.c_void_p), ("in_len", ctypes.c_void_p),
@@ -205,6 +218,9 @@ def load(path: str) -> ctypes.CDLL:
     L.sqobfs_quic_keyring_create_suite.argtypes = [vp, u32, u32, vp, ctypes.POINTER(vp)]
     L.sqobfs_quic_keyring_destroy.argtypes = [vp]
     L.sqobfs_quic_keyring_destroy.restype = None
+    L.sqobfs_quic_keyring_create_secrets.argtypes = [vp, u32, u32, vp, ctypes.POINTER(vp)]
+    L.sqobfs_quic_keyring_rekey.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.sqobfs_quic_key_phase.argtypes = [vp, vp, ctypes.POINTER(QuicBatch), vp, vp]
     L.sqobfs_quic_seal.argtypes = [vp, vp, ctypes.POINTER(QuicBatch), vp]
     L.sqobfs_quic_open.argtypes = [vp, vp, ctypes.POINTER(QuicBatch), vp]
     L.sqobfs_quic_seal_salamander.argtypes = [vp, vp, vp, ctypes.POINTER(QuicBatch), vp, vp]
@@ -817,6 +833,33 @@ class QuicKeyring:
         self.ctx = ctx
         self.count = len(keys)
 
+    @classmethod
+    def from_secrets(cls, ctx: Context, secrets: list[QuicSecret],
+                     suite: int = QUIC_CHACHA20_POLY1305) -> "QuicKeyring":
+        """Two entries per connection, derived on the device from its traffic
+        secret: entry 2c + (g & 1) holds connection c's generation g."""
+        arr = (QuicSecret * len(secrets))(*secrets)
+        h = ctypes.c_void_p()
+        _check(lib().sqobfs_quic_keyring_create_secrets(ctx.handle, suite, len(secrets), arr,
+                                                        ctypes.byref(h)),
+               "sqobfs_quic_keyring_create_secrets")
+        kr = cls.__new__(cls)
+        kr.suite, kr.handle, kr.ctx, kr.count = suite, h, ctx, 2 * len(secrets)
+        return kr
+
+    def rekey(self, conns: list[int], secrets: list[QuicSecret] | None = None,
+              stream=None) -> None:
+        """secrets None: a key update of each connection in conns (generation
+        g + 1 replaces g - 1); else the slots start again at generations 0
+        and 1 from the new secrets.  Returns when the keys are in place."""
+        idx = (ctypes.c_uint32 * len(conns))(*conns)
+        arr = None
+        if secrets is not None:
+            assert len(secrets) == len(conns)
+            arr = (QuicSecret * len(secrets))(*secrets)
+        _check(lib().sqobfs_quic_keyring_rekey(self.ctx.handle, self.handle, len(conns), idx, arr,
+                                               stream), "sqobfs_quic_keyring_rekey")
+
     def close(self) -> None:
         if self.handle:
             lib().sqobfs_quic_keyring_destroy(self.handle)
@@ -845,6 +888,14 @@ def quic_seal(ctx: Context, kr: QuicKeyring, batch: QuicBatch, stream=None) -> N
 def quic_open(ctx: Context, kr: QuicKeyring, batch: QuicBatch, stream=None) -> None:
     _check(lib().sqobfs_quic_open(ctx.handle, kr.handle, ctypes.byref(batch), stream),
            "sqobfs_quic_open")
+
+
+def quic_key_phase(ctx: Context, kr: QuicKeyring, batch: QuicBatch, key_id_out,
+                   stream=None) -> None:
+    """key_id_out[i] (device uint16) = the entry packet i needs: its key_id
+    with the low bit set to the packet's Key Phase bit."""
+    _check(lib().sqobfs_quic_key_phase(ctx.handle, kr.handle, ctypes.byref(batch),
+                                       _ptr(key_id_out), stream), "sqobfs_quic_key_phase")
 
 
 def quic_seal_salamander(ctx: Context, kr: QuicKeyring, okr: Keyring, batch: QuicBatch, salt,
