@@ -441,6 +441,69 @@ int sqobfs_quic_keyring_rekey(sqobfs_ctx *ctx, sqobfs_quic_keyring *kr, uint32_t
 int sqobfs_quic_key_phase(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
                           const sqobfs_quic_batch *b, uint16_t *key_id_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * QUIC v1 Initial packets (RFC 9001 5.2-5.4, AEAD_AES_128_GCM): opened and
+ * sealed with keys derived per packet on the device.  New symbols only: no
+ * struct above changes layout, so SQOBFS_ABI_VERSION stays as it is.
+ *
+ * Initial keys are HKDF of the client's first Destination Connection ID
+ * (quic-go internal/handshake/initial_aead.go), so a listener meets a new
+ * key with every new client and every probe.  There is no keyring: per
+ * packet the long header is parsed (RFC 9000 17.2.2), the keys are derived
+ * (HKDF-Extract with the v1 salt, "client in" / "server in", then "quic key",
+ * "quic iv", "quic hp") and the packet is opened or sealed, all on the
+ * device; nothing per packet happens on the host.
+ *
+ * b is used as sqobfs_quic_open / sqobfs_quic_seal use it (in, in_off,
+ * in_len, out, out_off, out_len, pn, pn_out; in place or disjoint, as there)
+ * except that b->pn_offset and b->key_id must be NULL: the header is parsed
+ * and there is no keyring.
+ *   side: whose keys protect the packets.  A server opens with
+ *     SQOBFS_QUIC_SIDE_CLIENT and seals with SQOBFS_QUIC_SIDE_SERVER, a
+ *     client the reverse.
+ *   odcid [n * 20], odcid_len [n] (device): the connection's original DCID
+ *     per packet, for packets whose keys cannot be read from them (every
+ *     seal by a server, every open by a client, a client's later Initials
+ *     after the server chose a new connection id).  Both NULL: each packet's
+ *     own DCID field is used.  A length above 20 rejects the packet
+ *     (SQOBFS_QUIC_EHEADER).
+ * SQ_EINVAL, before anything is launched: pn_offset or key_id not NULL, any
+ * other side, exactly one of odcid / odcid_len NULL.
+ *
+ * The header must be a v1 Initial: long form and fixed bit set, type bits
+ * 00, version 0x00000001, both connection-id lengths at most 20, the token
+ * length and Length varints in any encoding; anything else (QUIC v2, other
+ * versions and types, a packet number offset past 65,535) gives
+ * out_len[i] = SQOBFS_QUIC_EHEADER.  pn_offset is the byte after the Length
+ * field and the packet spans [0, pn_offset + Length) of the datagram.
+ *   open: a header that runs off the end, a span beyond in_len[i] or
+ *     shorter than pn_offset + 4 + 16 gives SQOBFS_QUIC_ESHORT, a bad tag
+ *     SQOBFS_QUIC_EAUTH.  Otherwise out = the unprotected header followed by
+ *     the plaintext, out_len[i] = span - 16, pn_out[i] = the packet number
+ *     decoded against pn[i] (0 for packets rejected before the tag check),
+ *     and, for opened packets only, pn_offset_out[i] and consumed[i] = span
+ *     (each pointer optional).  Bytes of a coalesced datagram after the span
+ *     are not read into out: the caller hands them to the next stage.
+ *   seal: in = the unprotected long header followed by the payload, all of
+ *     in_len[i]; the Length field must equal pn_len + payload + 16, else
+ *     SQOBFS_QUIC_EHEADER.  out_len[i] = in_len[i] + 16; pn_offset_out[i]
+ *     (optional) as for open.  The packet-number length comes from the
+ *     first byte.
+ * Hysteria2 wire datagrams are obfuscated: de-obfuscate them with the
+ * Salamander kernel first, as for sqobfs_quic_key_phase; there is no fused
+ * form.  Both calls queue two kernels on `stream` (NULL: the HIP null
+ * stream) and return without waiting. */
+#define SQOBFS_QUIC_EHEADER 0xFFFFFFFCu  /* not a well-formed v1 Initial */
+#define SQOBFS_QUIC_SIDE_CLIENT 0u       /* keys of "client in" */
+#define SQOBFS_QUIC_SIDE_SERVER 1u       /* keys of "server in" */
+
+int sqobfs_quic_initial_open(sqobfs_ctx *ctx, const sqobfs_quic_batch *b, uint32_t side,
+                             const uint8_t *odcid, const uint8_t *odcid_len,
+                             uint16_t *pn_offset_out, uint32_t *consumed, void *stream);
+int sqobfs_quic_initial_seal(sqobfs_ctx *ctx, const sqobfs_quic_batch *b, uint32_t side,
+                             const uint8_t *odcid, const uint8_t *odcid_len,
+                             uint16_t *pn_offset_out, void *stream);
+
 /* QUIC protection and the Salamander layer in ONE pass (Hysteria2's send and
  * receive path: quic-go seals a packet, then SalamanderPacketConn.WriteTo
  * obfuscates the datagram, salamander.go:57-70; ReadFrom then Open on the

@@ -53,6 +53,11 @@ struct sqobfs_ctx {
   // two threads on one stream cannot interleave their group / kernel pairs.
   std::mutex gcm_mu;
   std::unordered_map<hipStream_t, std::pair<void *, uint64_t>> gcm_scratch;
+  // QUIC Initial packets (sq_quic_initial.hip): the per-packet key records,
+  // cached per stream as gcm_scratch is and guarded by gcm_mu (the two
+  // kernels of a call share them), and the device AES T-table
+  std::unordered_map<hipStream_t, std::pair<void *, uint64_t>> init_ws;
+  uint32_t *init_t0 = nullptr;
 };
 
 namespace {
@@ -285,6 +290,11 @@ void sq_ctx_stream_destroy(sqobfs_ctx *ctx, void *s) {
     if (it != ctx->gcm_scratch.end()) {
       tab_free(it->second.first);  // (the stream is idle)
       ctx->gcm_scratch.erase(it);
+    }
+    auto iw = ctx->init_ws.find((hipStream_t)s);
+    if (iw != ctx->init_ws.end()) {
+      tab_free(iw->second.first);
+      ctx->init_ws.erase(iw);
     }
   }
   (void)hipStreamDestroy((hipStream_t)s);
@@ -741,6 +751,9 @@ void sqobfs_close(sqobfs_ctx *ctx) {
   (void)hipStreamSynchronize(ctx->rel);  // keyrings released before the context
   for (auto &kv : ctx->gcm_scratch)
     tab_free(kv.second.first);
+  for (auto &kv : ctx->init_ws)
+    tab_free(kv.second.first);
+  tab_free(ctx->init_t0);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->dev) (void)hipFree(ctx->dev);
   (void)hipStreamDestroy(ctx->stream);
@@ -1606,6 +1619,169 @@ int sqobfs_quic_seal(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr, const sqobf
 int sqobfs_quic_open(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr, const sqobfs_quic_batch *b,
                      void *stream) {
   return quic_launch(1, ctx, kr, b, stream);
+}
+
+// ---- QUIC Initial packets: keys derived per packet on the device
+extern "C++" {
+namespace {
+// A QUIC version's Initial constants (RFC 9001 5.2) in the form the key
+// kernel takes them: the salt as the HMAC pad midstates of HKDF-Extract, each
+// label as the padded SHA-256 block that follows the inner pad.
+struct InitialConsts {
+  uint32_t version;
+  uint32_t salt_im[8], salt_om[8];
+  uint32_t side_msg[2][16];  // SQOBFS_QUIC_SIDE_CLIENT, _SERVER
+  uint32_t key_msg[16], iv_msg[16], hp_msg[16];
+};
+
+// HKDF-Expand-Label(., label, "", L) (RFC 8446 7.1) with HKDF-Expand's
+// counter byte, SHA-256's pad byte and the bit length of pad block + message
+void label_block(const char *label, uint32_t L, uint32_t (&m)[16]) {
+  uint8_t b[64] = {0};
+  const size_t ll = strlen(label);
+  size_t n = 0;
+  b[n++] = (uint8_t)(L >> 8);
+  b[n++] = (uint8_t)L;
+  b[n++] = (uint8_t)(6 + ll);
+  memcpy(b + n, "tls13 ", 6);
+  n += 6;
+  memcpy(b + n, label, ll);
+  n += ll;
+  b[n++] = 0;     // empty context
+  b[n++] = 0x01;  // T(1)
+  b[n] = 0x80;
+  const uint32_t bits = (uint32_t)(64 + n) * 8;
+  b[62] = (uint8_t)(bits >> 8);
+  b[63] = (uint8_t)bits;
+  for (int i = 0; i < 16; i++)
+    m[i] = (uint32_t)b[4 * i] << 24 | (uint32_t)b[4 * i + 1] << 16 | (uint32_t)b[4 * i + 2] << 8 |
+           b[4 * i + 3];
+}
+
+InitialConsts initial_consts(uint32_t version, const uint8_t *salt, size_t salt_len,
+                             const char *key, const char *iv, const char *hp) {
+  InitialConsts c;
+  c.version = version;
+  uint8_t k[64] = {0};
+  memcpy(k, salt, salt_len);
+  for (int pass = 0; pass < 2; pass++) {
+    uint32_t m[16], *st = pass ? c.salt_om : c.salt_im;
+    const uint32_t pad = pass ? 0x5c5c5c5cu : 0x36363636u;
+    for (int i = 0; i < 16; i++)
+      m[i] = ((uint32_t)k[4 * i] << 24 | (uint32_t)k[4 * i + 1] << 16 |
+              (uint32_t)k[4 * i + 2] << 8 | k[4 * i + 3]) ^ pad;
+    const uint32_t iv256[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                               0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+    memcpy(st, iv256, sizeof iv256);
+    sq::cpu::s2_compress(st, m);
+  }
+  label_block("client in", 32, c.side_msg[SQOBFS_QUIC_SIDE_CLIENT]);
+  label_block("server in", 32, c.side_msg[SQOBFS_QUIC_SIDE_SERVER]);
+  label_block(key, 16, c.key_msg);
+  label_block(iv, 12, c.iv_msg);
+  label_block(hp, 16, c.hp_msg);
+  return c;
+}
+
+const InitialConsts &initial_v1() {
+  static const uint8_t salt[20] = {0x38, 0x76, 0x2c, 0xf7, 0xf5, 0x59, 0x34, 0xb3, 0x4d, 0x17,
+                                   0x9a, 0xe6, 0xa4, 0xc8, 0x0c, 0xad, 0xcc, 0xbb, 0x7f, 0x0a};
+  static const InitialConsts c =
+      initial_consts(0x00000001u, salt, sizeof salt, "quic key", "quic iv", "quic hp");
+  return c;
+}
+
+int quic_initial_launch(int open, sqobfs_ctx *ctx, const sqobfs_quic_batch *b, uint32_t side,
+                        const uint8_t *odcid, const uint8_t *odcid_len, uint16_t *pn_offset_out,
+                        uint32_t *consumed, void *stream) {
+  if (!ctx || !b || b->flags || b->pn_offset || b->key_id) return SQ_EINVAL;
+  if (side != SQOBFS_QUIC_SIDE_CLIENT && side != SQOBFS_QUIC_SIDE_SERVER) return SQ_EINVAL;
+  if ((odcid == nullptr) != (odcid_len == nullptr)) return SQ_EINVAL;
+  if (b->n == 0) return SQ_OK;
+  if (!b->in || !b->in_off || !b->in_len || !b->out || !b->out_off || !b->out_len || !b->pn)
+    return SQ_EINVAL;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  const InitialConsts &c = initial_v1();
+  sq::QInitParams ip;
+  memset(&ip, 0, sizeof ip);
+  ip.in = b->in;
+  ip.in_off = b->in_off;
+  ip.in_len = b->in_len;
+  ip.out = b->out;
+  ip.out_off = b->out_off;
+  ip.out_len = b->out_len;
+  ip.pn = b->pn;
+  ip.pn_out = open ? b->pn_out : nullptr;
+  ip.odcid = odcid;
+  ip.odcid_len = odcid_len;
+  ip.pn_offset_out = pn_offset_out;
+  ip.consumed = open ? consumed : nullptr;
+  ip.n = b->n;
+  ip.open = open ? 1u : 0u;
+  ip.version = c.version;
+  memcpy(ip.salt_im, c.salt_im, sizeof ip.salt_im);
+  memcpy(ip.salt_om, c.salt_om, sizeof ip.salt_om);
+  memcpy(ip.side_msg, c.side_msg[side], sizeof ip.side_msg);
+  memcpy(ip.key_msg, c.key_msg, sizeof ip.key_msg);
+  memcpy(ip.iv_msg, c.iv_msg, sizeof ip.iv_msg);
+  memcpy(ip.hp_msg, c.hp_msg, sizeof ip.hp_msg);
+  hipStream_t s = pick_stream(ctx, stream);
+  // held over both launches: two threads on one stream share its records
+  std::lock_guard<std::mutex> lk(ctx->gcm_mu);
+  if (!ctx->init_t0) {  // once per context; waited for, as any stream may use it next
+    uint32_t *t0 = nullptr;
+    hipError_t e = tab_alloc((void **)&t0, sizeof(uint32_t) * 256, s);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(t0, aes_tables().t0, sizeof(uint32_t) * 256, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      tab_free_async(t0, s);
+      return hip_status(e);
+    }
+    ctx->init_t0 = t0;
+  }
+  ip.t0 = ctx->init_t0;
+  // the records: cached per library-owned stream (grown as needed, the old
+  // block freed in stream order), else allocated for this call
+  const uint64_t bytes = (uint64_t)b->n * sizeof(sq::QInitRec);
+  void *ws = nullptr;
+  const bool cached = s == ctx->stream || ctx->gcm_scratch.count(s);
+  if (cached) {
+    auto &e = ctx->init_ws[s];
+    if (e.second < bytes) {
+      const uint64_t want = std::max<uint64_t>(bytes, 2 * e.second);
+      tab_free_async(e.first, s);
+      e = {nullptr, 0};
+      if (tab_alloc(&e.first, want, s) == hipSuccess) e.second = want;
+      else e.first = nullptr;
+    }
+    ws = e.first;
+  } else if (tab_alloc(&ws, bytes, s) != hipSuccess) {
+    ws = nullptr;
+  }
+  if (!ws) {
+    (void)hipGetLastError();
+    return SQ_ENOMEM;
+  }
+  ip.rec = (sq::QInitRec *)ws;
+  const int st = sq_launch_quic_initial(&ip, s);
+  if (!cached) tab_free_async(ws, s);
+  return st;
+}
+}  // namespace
+}  // extern "C++"
+
+int sqobfs_quic_initial_open(sqobfs_ctx *ctx, const sqobfs_quic_batch *b, uint32_t side,
+                             const uint8_t *odcid, const uint8_t *odcid_len,
+                             uint16_t *pn_offset_out, uint32_t *consumed, void *stream) {
+  return quic_initial_launch(1, ctx, b, side, odcid, odcid_len, pn_offset_out, consumed, stream);
+}
+
+int sqobfs_quic_initial_seal(sqobfs_ctx *ctx, const sqobfs_quic_batch *b, uint32_t side,
+                             const uint8_t *odcid, const uint8_t *odcid_len,
+                             uint16_t *pn_offset_out, void *stream) {
+  return quic_initial_launch(0, ctx, b, side, odcid, odcid_len, pn_offset_out, nullptr, stream);
 }
 
 size_t sqobfs_host_staging_bytes(const sqobfs_ctx *ctx) { return ctx ? ctx->pinned_cap : 0; }

@@ -211,7 +211,52 @@ struct QPhaseParams {
   uint32_t suite;
 };
 
+// QUIC Initial packets (sq_quic_initial.hip): the per-packet record that the
+// key kernel writes into the context's workspace and the packet kernel reads.
+struct alignas(16) QInitRec {
+  uint32_t rk[44];     // AES-128 schedule of the packet key, rounds 1..9 rotated
+                       // by 16 bits (sq_quic_aes.h aes_encrypt_n)
+  uint32_t iv[3];
+  uint32_t err;        // 0, or the SQOBFS_QUIC_E* code the packet ends with
+  uint32_t hp[4];      // header-protection key, not expanded
+  uint32_t h[4][4];    // H^1 .. H^4, big-endian words (SP 800-38D bit order)
+  uint32_t pn_offset;  // the byte after the Length field
+  uint32_t span;       // open: pn_offset + Length, the packet's bytes
+  uint32_t pad[2];
+};
+static_assert(sizeof(QInitRec) == 288, "QInitRec layout");
+
+// One launch pair.  The version's constants are data: the salt as the HMAC
+// pad midstates of HKDF-Extract, and each label as the padded SHA-256 block
+// that follows the inner pad (Expand-Label info || 0x01 || 0x80 .. length).
+struct QInitParams {
+  const uint8_t *in;
+  const uint64_t *in_off;
+  const uint32_t *in_len;
+  uint8_t *out;
+  const uint64_t *out_off;
+  uint32_t *out_len;
+  const uint64_t *pn;
+  uint64_t *pn_out;
+  const uint8_t *odcid;      // [n * 20] or NULL: the packet's own DCID
+  const uint8_t *odcid_len;  // [n]
+  uint16_t *pn_offset_out;   // or NULL
+  uint32_t *consumed;        // open: or NULL
+  QInitRec *rec;             // [n] workspace
+  const uint32_t *t0;        // AES T-table (256 words)
+  uint32_t n;
+  uint32_t open;
+  uint32_t version;          // the version field the header must carry
+  uint32_t pad_;
+  uint32_t salt_im[8], salt_om[8];
+  uint32_t side_msg[16];     // "client in" or "server in", 32 bytes
+  uint32_t key_msg[16], iv_msg[16], hp_msg[16];
+};
+
 }  // namespace sq
+
+// launcher implemented in sq_quic_initial.hip: both kernels on `stream`
+extern "C" int sq_launch_quic_initial(const sq::QInitParams *ip, void *stream);
 
 // launchers implemented in sq_quic_keys.hip
 extern "C" int sq_launch_quic_rekey(const sq::QKeysParams *kp, void *stream);

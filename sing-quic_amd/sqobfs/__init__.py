@@ -125,6 +125,8 @@ class QuicBatch(ctypes.Structure):
 
 QUIC_EKEY, QUIC_ESHORT, QUIC_EAUTH = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD
 QUIC_CHACHA20_POLY1305, QUIC_AES_128_GCM, QUIC_AES_256_GCM = 0, 1, 2  # SQOBFS_QUIC_* suites
+QUIC_EHEADER = 0xFFFFFFFC  # Initial packets: not a well-formed v1 Initial
+QUIC_SIDE_CLIENT, QUIC_SIDE_SERVER = 0, 1  # whose Initial keys protect the packets
 
 
 class UdpView(ctypes.Structure):
@@ -221,6 +223,8 @@ def load(path: str) -> ctypes.CDLL:
     L.sqobfs_quic_keyring_create_secrets.argtypes = [vp, u32, u32, vp, ctypes.POINTER(vp)]
     L.sqobfs_quic_keyring_rekey.argtypes = [vp, vp, u32, vp, vp, vp]
     L.sqobfs_quic_key_phase.argtypes = [vp, vp, ctypes.POINTER(QuicBatch), vp, vp]
+    L.sqobfs_quic_initial_open.argtypes = [vp, ctypes.POINTER(QuicBatch), u32, vp, vp, vp, vp, vp]
+    L.sqobfs_quic_initial_seal.argtypes = [vp, ctypes.POINTER(QuicBatch), u32, vp, vp, vp, vp]
     L.sqobfs_quic_seal.argtypes = [vp, vp, ctypes.POINTER(QuicBatch), vp]
     L.sqobfs_quic_open.argtypes = [vp, vp, ctypes.POINTER(QuicBatch), vp]
     L.sqobfs_quic_seal_salamander.argtypes = [vp, vp, vp, ctypes.POINTER(QuicBatch), vp, vp]
@@ -896,6 +900,28 @@ def quic_key_phase(ctx: Context, kr: QuicKeyring, batch: QuicBatch, key_id_out,
     with the low bit set to the packet's Key Phase bit."""
     _check(lib().sqobfs_quic_key_phase(ctx.handle, kr.handle, ctypes.byref(batch),
                                        _ptr(key_id_out), stream), "sqobfs_quic_key_phase")
+
+
+def quic_initial_open(ctx: Context, batch: QuicBatch, side: int, odcid=None, odcid_len=None,
+                      pn_offset_out=None, consumed=None, stream=None) -> None:
+    """Open QUIC v1 Initial packets with keys derived per packet on the device
+    (no keyring; batch.pn_offset and batch.key_id stay None).  side: whose
+    keys protect them (QUIC_SIDE_CLIENT for a server's receive path).  odcid
+    (device uint8 [n*20]) and odcid_len ([n]): the original DCIDs, or both
+    None to use each packet's own.  pn_offset_out (uint16) and consumed
+    (uint32, the packet's span in its datagram) are written for opened packets."""
+    _check(lib().sqobfs_quic_initial_open(ctx.handle, ctypes.byref(batch), side, _ptr(odcid),
+                                          _ptr(odcid_len), _ptr(pn_offset_out), _ptr(consumed),
+                                          stream), "sqobfs_quic_initial_open")
+
+
+def quic_initial_seal(ctx: Context, batch: QuicBatch, side: int, odcid=None, odcid_len=None,
+                      pn_offset_out=None, stream=None) -> None:
+    """Seal QUIC v1 Initial packets (in = unprotected long header || payload,
+    Length field = pn_len + payload + 16); arguments as quic_initial_open."""
+    _check(lib().sqobfs_quic_initial_seal(ctx.handle, ctypes.byref(batch), side, _ptr(odcid),
+                                          _ptr(odcid_len), _ptr(pn_offset_out), stream),
+           "sqobfs_quic_initial_seal")
 
 
 def quic_seal_salamander(ctx: Context, kr: QuicKeyring, okr: Keyring, batch: QuicBatch, salt,
