@@ -436,8 +436,8 @@ int sqobfs_quic_keyring_rekey(sqobfs_ctx *ctx, sqobfs_quic_keyring *kr, uint32_t
  * then be passed as key_id of sqobfs_quic_open in the same stream.  Works
  * for every keyring whose entry pairs share hp; for keyrings not made from
  * secrets the pairing is the caller's convention.  Wire datagrams of the
- * fused Salamander path are obfuscated: de-obfuscate them first and use
- * sqobfs_quic_open, there is no fused resolver. */
+ * fused Salamander path are obfuscated: they take
+ * sqobfs_quic_key_phase_salamander (below, with the fused calls). */
 int sqobfs_quic_key_phase(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
                           const sqobfs_quic_batch *b, uint16_t *key_id_out, void *stream);
 
@@ -489,10 +489,11 @@ int sqobfs_quic_key_phase(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
  *     SQOBFS_QUIC_EHEADER.  out_len[i] = in_len[i] + 16; pn_offset_out[i]
  *     (optional) as for open.  The packet-number length comes from the
  *     first byte.
- * Hysteria2 wire datagrams are obfuscated: de-obfuscate them with the
- * Salamander kernel first, as for sqobfs_quic_key_phase; there is no fused
- * form.  Both calls queue two kernels on `stream` (NULL: the HIP null
- * stream) and return without waiting. */
+ * Hysteria2 wire datagrams are obfuscated: they take
+ * sqobfs_quic_initial_open_salamander / _seal_salamander (below, with the
+ * fused calls), which remove or add the Salamander layer in the same pass.
+ * Both calls queue two kernels on `stream` (NULL: the HIP null stream) and
+ * return without waiting. */
 #define SQOBFS_QUIC_EHEADER 0xFFFFFFFCu  /* not a well-formed v1 Initial */
 #define SQOBFS_QUIC_SIDE_CLIENT 0u       /* keys of "client in" */
 #define SQOBFS_QUIC_SIDE_SERVER 1u       /* keys of "server in" */
@@ -527,6 +528,55 @@ int sqobfs_quic_seal_salamander(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
 int sqobfs_quic_open_salamander(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
                                 const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
                                 void *stream);
+
+/* The Key Phase resolver on wire datagrams of the fused path: b is used as
+ * sqobfs_quic_open_salamander uses it (in = wire datagrams, salt first;
+ * pn_offset relative to the QUIC packet), okr as there.  The result rules are
+ * those of sqobfs_quic_key_phase, applied to the de-obfuscated packet; a
+ * datagram shorter than the salt keeps key_id[i].  key_id_out then feeds
+ * sqobfs_quic_open_salamander on the same stream.  All suites.  SQ_EINVAL as
+ * sqobfs_quic_key_phase, and for okr NULL, not a Salamander keyring or of
+ * another context. */
+int sqobfs_quic_key_phase_salamander(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
+                                     const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
+                                     uint16_t *key_id_out, void *stream);
+
+/* Initial packets under the Salamander layer, in one pass (a Hysteria2
+ * listener's first datagram of every new client): sqobfs_quic_initial_open /
+ * _seal composed with the layer as the fused pair above composes it.  okr: a
+ * Salamander keyring, entry 0 is the PSK.  Keystream byte k of K_i covers
+ * byte k mod 32 of the QUIC packet (the XOR starts right after the salt);
+ * pn_offset_out, consumed and every offset are relative to the QUIC packet,
+ * not the wire datagram.
+ *   open: in = wire datagram (in_len[i] bytes, salt first).  out, out_len[i]
+ *     = span - 16, pn_out, pn_offset_out and consumed[i] = span as
+ *     sqobfs_quic_initial_open on the de-obfuscated packet, with its error
+ *     codes; in_len[i] < 8 or nothing after the salt gives
+ *     SQOBFS_QUIC_ESHORT.  For an opened packet the de-obfuscated bytes
+ *     [span, in_len[i] - 8) of the datagram (coalesced packets) are written
+ *     to out[span, in_len[i] - 8), their own offset: the next packet starts
+ *     at out + consumed[i] and needs no second Salamander pass (the 16 bytes
+ *     before it are undefined).  For rejected packets nothing beyond out_len
+ *     is promised.  In place (out_off == in_off) and disjoint both work.
+ *   seal: in = the unprotected long header followed by the payload; out =
+ *     salt[i] || (protected packet || tag) ^ K_i, out_len[i] = in_len[i] +
+ *     24.  salt: [n*8] device bytes.  out is disjoint from in, or the
+ *     in-place form out_off[i] == in_off[i] - 8.  One Initial per datagram:
+ *     a caller that coalesces packets behind it seals with
+ *     sqobfs_quic_initial_seal and obfuscates the datagram afterwards.
+ * SQ_EINVAL before anything is launched: everything the unfused calls
+ * refuse, okr NULL, not a Salamander keyring or of another context, seal
+ * with salt NULL. */
+int sqobfs_quic_initial_open_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                                        const sqobfs_quic_batch *b, uint32_t side,
+                                        const uint8_t *odcid, const uint8_t *odcid_len,
+                                        uint16_t *pn_offset_out, uint32_t *consumed,
+                                        void *stream);
+int sqobfs_quic_initial_seal_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                                        const sqobfs_quic_batch *b, uint32_t side,
+                                        const uint8_t *odcid, const uint8_t *odcid_len,
+                                        const uint8_t *salt, uint16_t *pn_offset_out,
+                                        void *stream);
 
 /* ------------------------------------------------------------------------
  * Several GPUs in one process (packets are independent, so a

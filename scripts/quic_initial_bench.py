@@ -8,8 +8,15 @@ One process, repetitions alternating between the routes, median and spread:
            then sqobfs_quic_open with key ids
   onekey   sqobfs_quic_open of packets of the same sizes under one key: the
            floor that per-packet keys are paid over
-Prints one JSON line and writes it to --out.  `--only new` runs that route
-alone (under a kernel trace it gives the split between the two kernels).
+The same batch wrapped in the Salamander layer:
+  two-step sqobfs.launch de-obfuscates into a scratch buffer, then
+           sqobfs_quic_initial_open; seal in the reverse order
+  fused    sqobfs_quic_initial_open_salamander / _seal_salamander
+and, `--phase`, sqobfs_quic_key_phase_salamander against the
+sqobfs_quic_open_salamander it precedes, per suite, on N short-header packets.
+Prints one JSON line and writes it to --out.  `--only new` / `--only fused`
+runs that route alone (under a kernel trace it gives the split between the
+kernels).
 """
 from __future__ import annotations
 
@@ -55,7 +62,8 @@ def main():
     ap.add_argument("--n", type=int, default=65535)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--keyring-reps", type=int, default=3)
-    ap.add_argument("--only", choices=["new"], default=None)
+    ap.add_argument("--only", choices=["new", "fused"], default=None)
+    ap.add_argument("--phase", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -107,6 +115,74 @@ def main():
             for _ in range(a.reps):
                 timed(new_seal), timed(new_open)
             return
+        # the same batch under the Salamander layer: datagrams of DGRAM + 8 bytes
+        okr = sqobfs.Keyring(ctx, sqobfs.SALAMANDER, [b"sing-quic-mi355x-bench-psk"])
+        d_salt = t(rng.integers(0, 256, n * 8, dtype=np.uint8))
+        d_ow, d_ow2 = t(np.zeros(n * SLOT, np.uint8)), t(np.zeros(n * SLOT, np.uint8))
+        len_ow, len_tmp = t(np.full(n, DGRAM + 8, np.uint32)), t(np.zeros(n, np.uint32))
+        bf_seal = sqobfs.quic_batch(n, d_plain, off, len_p, d_ow, off, out_len, None, d_pn)
+        bf_open = sqobfs.quic_batch(n, d_ow, off, len_ow, d_back, off, out_len, None, d_largest,
+                                    None, pn_out)
+        b_obf = sqobfs.make_batch(n, d_wire, off, len_w, d_ow2, off, len_tmp, salt=d_salt)
+        b_deo = sqobfs.make_batch(n, d_ow, off, len_ow, d_wire, off, len_tmp)
+        side = sqobfs.QUIC_SIDE_CLIENT
+        fused_seal = lambda: sqobfs.quic_initial_seal_salamander(ctx, okr, bf_seal, side, d_salt)  # noqa: E731
+        fused_open = lambda: sqobfs.quic_initial_open_salamander(ctx, okr, bf_open, side)  # noqa: E731
+
+        def two_seal():  # d_plain -> d_wire -> d_ow2
+            new_seal()
+            sqobfs.launch(ctx, okr, sqobfs.OBFUSCATE, b_obf)
+
+        def two_open():  # d_ow -> d_wire -> d_back
+            sqobfs.launch(ctx, okr, sqobfs.DEOBFUSCATE, b_deo)
+            new_open()
+
+        timed(fused_seal), timed(two_seal)
+        assert bool((out_len == DGRAM).all()) and torch.equal(d_ow, d_ow2), "the routes differ"
+        for fn in (fused_open, two_open):
+            d_back.zero_()
+            timed(fn)
+            assert bool((out_len == DGRAM - 16).all()) and bool((pn_out == d_pn).all())
+            assert torch.equal(d_back.view(n, SLOT)[:, :DGRAM - 16], want)
+        if a.only == "fused":
+            for _ in range(a.reps):
+                timed(fused_seal), timed(fused_open)
+            return
+        TS = {"fused_open": [], "two_step_open": [], "fused_seal": [], "two_step_seal": []}
+        for r in range(a.reps):
+            TS["fused_open"].append(timed(fused_open))
+            TS["two_step_open"].append(timed(two_open))
+            TS["fused_seal"].append(timed(fused_seal))
+            TS["two_step_seal"].append(timed(two_seal))
+        res.update({k: spread(v) for k, v in TS.items()})
+        if a.phase:  # two generations of one connection, random phases, pn_offset 9
+            ph = rng.integers(0, 2, n).astype(np.uint16)
+            plain[:, 0], plain[:, 9:13] = 0x43 | (ph << 2), 0
+            d_short, d_ph, pno9 = t(plain.reshape(-1)), t(ph), t(np.full(n, 9, np.uint16))
+            ids, zero = t(np.zeros(n, np.uint16)), t(np.zeros(n, np.uint64))
+            for name, suite, hl in (("chacha20", sqobfs.QUIC_CHACHA20_POLY1305, 32),
+                                    ("aes128", sqobfs.QUIC_AES_128_GCM, 32),
+                                    ("aes256", sqobfs.QUIC_AES_256_GCM, 48)):
+                with QuicKeyring.from_secrets(ctx, [sqobfs.QuicSecret.of(bytes(range(hl)))],
+                                              suite) as kr:
+                    bs = sqobfs.quic_batch(n, d_short, off, len_p, d_ow, off, out_len, pno9, zero,
+                                           d_ph)
+                    bo = sqobfs.quic_batch(n, d_ow, off, len_ow, d_back, off, out_len, pno9, zero,
+                                           None, pn_out)
+                    bo2 = sqobfs.quic_batch(n, d_ow, off, len_ow, d_back, off, out_len, pno9, zero,
+                                            ids, pn_out)
+                    sqobfs.quic_seal_salamander(ctx, kr, okr, bs, d_salt)
+                    resolve = lambda: sqobfs.quic_key_phase_salamander(ctx, kr, okr, bo, ids)  # noqa: E731
+                    opn = lambda: sqobfs.quic_open_salamander(ctx, kr, okr, bo2)  # noqa: E731
+                    timed(resolve), timed(opn)
+                    assert torch.equal(ids, d_ph) and bool((out_len == DGRAM - 16).all())
+                    tp, to = [], []
+                    for _ in range(a.reps):
+                        tp.append(timed(resolve))
+                        to.append(timed(opn))
+                    res["phase_" + name] = {"key_phase_salamander": spread(tp),
+                                            "open_salamander": spread(to)}
+        okr.close()
         # the keyring route, end to end (also the warm-up of its kernels)
         b_kr = sqobfs.quic_batch(n, d_wire, off, len_w, d_back, off, out_len, pno, d_largest, kid,
                                  pn_out)

@@ -1455,9 +1455,11 @@ int sqobfs_quic_keyring_create_secrets(sqobfs_ctx *ctx, uint32_t suite, uint32_t
   return SQ_OK;
 }
 
-int sqobfs_quic_key_phase(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
-                          const sqobfs_quic_batch *b, uint16_t *key_id_out, void *stream) {
+static int quic_key_phase_launch(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
+                                 const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
+                                 uint16_t *key_id_out, void *stream) {
   if (!ctx || !kr || kr->ctx != ctx || !b || b->flags || !key_id_out) return SQ_EINVAL;
+  if (okr && (okr->ctx != ctx || okr->kind != SQOBFS_SALAMANDER)) return SQ_EINVAL;
   if (b->n == 0) return SQ_OK;
   if (!b->in || !b->in_off || !b->in_len || !b->pn_offset) return SQ_EINVAL;
   DeviceScope ds_(ctx->device);
@@ -1476,10 +1478,29 @@ int sqobfs_quic_key_phase(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
   pp.n = b->n;
   pp.n_keys = kr->count;
   pp.suite = kr->suite;
+  if (okr) {
+    pp.obfs = 1;
+    pp.opsk = okr->host0;
+  }
   hipStream_t s = pick_stream(ctx, stream);
   const int st = sq_launch_quic_key_phase(&pp, s);
-  if (st == SQ_OK) kr->uses.note(s);
+  if (st == SQ_OK) {
+    kr->uses.note(s);
+    if (okr) okr->uses.note(s);
+  }
   return st;
+}
+
+int sqobfs_quic_key_phase(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
+                          const sqobfs_quic_batch *b, uint16_t *key_id_out, void *stream) {
+  return quic_key_phase_launch(ctx, kr, nullptr, b, key_id_out, stream);
+}
+
+int sqobfs_quic_key_phase_salamander(sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
+                                     const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
+                                     uint16_t *key_id_out, void *stream) {
+  if (!okr) return SQ_EINVAL;
+  return quic_key_phase_launch(ctx, kr, okr, b, key_id_out, stream);
 }
 
 static int quic_launch(int open, sqobfs_ctx *ctx, const sqobfs_quic_keyring *kr,
@@ -1693,8 +1714,11 @@ const InitialConsts &initial_v1() {
 
 int quic_initial_launch(int open, sqobfs_ctx *ctx, const sqobfs_quic_batch *b, uint32_t side,
                         const uint8_t *odcid, const uint8_t *odcid_len, uint16_t *pn_offset_out,
-                        uint32_t *consumed, void *stream) {
+                        uint32_t *consumed, void *stream, const sqobfs_keyring *okr = nullptr,
+                        const uint8_t *salt = nullptr) {
   if (!ctx || !b || b->flags || b->pn_offset || b->key_id) return SQ_EINVAL;
+  if (okr && (okr->ctx != ctx || okr->kind != SQOBFS_SALAMANDER || (!open && !salt)))
+    return SQ_EINVAL;
   if (side != SQOBFS_QUIC_SIDE_CLIENT && side != SQOBFS_QUIC_SIDE_SERVER) return SQ_EINVAL;
   if ((odcid == nullptr) != (odcid_len == nullptr)) return SQ_EINVAL;
   if (b->n == 0) return SQ_OK;
@@ -1720,6 +1744,11 @@ int quic_initial_launch(int open, sqobfs_ctx *ctx, const sqobfs_quic_batch *b, u
   ip.n = b->n;
   ip.open = open ? 1u : 0u;
   ip.version = c.version;
+  if (okr) {  // the fused Salamander layer: entry 0 of the keyring's device table
+    ip.obfs = 1;
+    ip.salt = salt;
+    ip.opsk = okr->table;
+  }
   memcpy(ip.salt_im, c.salt_im, sizeof ip.salt_im);
   memcpy(ip.salt_om, c.salt_om, sizeof ip.salt_om);
   memcpy(ip.side_msg, c.side_msg[side], sizeof ip.side_msg);
@@ -1744,7 +1773,11 @@ int quic_initial_launch(int open, sqobfs_ctx *ctx, const sqobfs_quic_batch *b, u
   ip.t0 = ctx->init_t0;
   // the records: cached per library-owned stream (grown as needed, the old
   // block freed in stream order), else allocated for this call
-  const uint64_t bytes = (uint64_t)b->n * sizeof(sq::QInitRec);
+  // then, fused, the packets' 32-byte Salamander keys.  One size for both
+  // routes: a caller's stream takes its block from the device pool per call,
+  // and calls that alternate between two sizes miss the pool's free block
+  // (measured: about 300 us per call at 65,535 packets)
+  const uint64_t bytes = (uint64_t)b->n * (sizeof(sq::QInitRec) + 32);
   void *ws = nullptr;
   const bool cached = s == ctx->stream || ctx->gcm_scratch.count(s);
   if (cached) {
@@ -1767,6 +1800,7 @@ int quic_initial_launch(int open, sqobfs_ctx *ctx, const sqobfs_quic_batch *b, u
   ip.rec = (sq::QInitRec *)ws;
   const int st = sq_launch_quic_initial(&ip, s);
   if (!cached) tab_free_async(ws, s);
+  if (st == SQ_OK && okr) okr->uses.note(s);
   return st;
 }
 }  // namespace
@@ -1782,6 +1816,26 @@ int sqobfs_quic_initial_seal(sqobfs_ctx *ctx, const sqobfs_quic_batch *b, uint32
                              const uint8_t *odcid, const uint8_t *odcid_len,
                              uint16_t *pn_offset_out, void *stream) {
   return quic_initial_launch(0, ctx, b, side, odcid, odcid_len, pn_offset_out, nullptr, stream);
+}
+
+int sqobfs_quic_initial_open_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                                        const sqobfs_quic_batch *b, uint32_t side,
+                                        const uint8_t *odcid, const uint8_t *odcid_len,
+                                        uint16_t *pn_offset_out, uint32_t *consumed,
+                                        void *stream) {
+  if (!okr) return SQ_EINVAL;
+  return quic_initial_launch(1, ctx, b, side, odcid, odcid_len, pn_offset_out, consumed, stream,
+                             okr);
+}
+
+int sqobfs_quic_initial_seal_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                                        const sqobfs_quic_batch *b, uint32_t side,
+                                        const uint8_t *odcid, const uint8_t *odcid_len,
+                                        const uint8_t *salt, uint16_t *pn_offset_out,
+                                        void *stream) {
+  if (!okr) return SQ_EINVAL;
+  return quic_initial_launch(0, ctx, b, side, odcid, odcid_len, pn_offset_out, nullptr, stream,
+                             okr, salt);
 }
 
 size_t sqobfs_host_staging_bytes(const sqobfs_ctx *ctx) { return ctx ? ctx->pinned_cap : 0; }

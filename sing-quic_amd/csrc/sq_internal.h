@@ -209,6 +209,8 @@ struct QPhaseParams {
   uint32_t n;
   uint32_t n_keys;
   uint32_t suite;
+  uint32_t obfs;  // 1: wire datagrams under the Salamander layer (as QParams)
+  PskEntry opsk;  // the Salamander keyring's entry 0
 };
 
 // QUIC Initial packets (sq_quic_initial.hip): the per-packet record that the
@@ -247,10 +249,16 @@ struct QInitParams {
   uint32_t n;
   uint32_t open;
   uint32_t version;          // the version field the header must carry
-  uint32_t pad_;
+  uint32_t obfs;             // 1: fused Salamander layer (as QParams); the packets'
+                             // 32-byte Salamander keys follow the n records
   uint32_t salt_im[8], salt_om[8];
   uint32_t side_msg[16];     // "client in" or "server in", 32 bytes
   uint32_t key_msg[16], iv_msg[16], hp_msg[16];
+  const uint8_t *salt;       // fused seal: [n*8] Salamander salts (device)
+  // The Salamander keyring's entry 0 in its device table.  Not by value as in
+  // QParams: these kernels' scalar registers are full of HKDF constants, and a
+  // kernarg segment 352 bytes longer cost quic_initial_keys<false> 11 VGPRs.
+  const PskEntry *opsk;
 };
 
 }  // namespace sq

@@ -11,8 +11,10 @@
 // client's first Destination Connection ID, so a listening port meets a new
 // key with every new client and every probe: there is no keyring here, and
 // no per-key table that a later packet could reuse.  Hysteria2 wire
-// datagrams are de-obfuscated with the Salamander kernel first, as for
-// sqobfs_quic_key_phase: there is no fused form.
+// datagrams (salt8 || packet ^ BLAKE2b-256(psk || salt8)) take the OB
+// instantiations of both kernels (sqobfs_quic_initial_open_salamander /
+// _seal_salamander): the Salamander layer comes off, or goes on, in the same
+// pass, with no launch and no buffer in between.
 //
 // Work decomposition, two kernels per call:
 //   1. quic_initial_keys: one lane per packet, 64 packets per wave.  The
@@ -38,12 +40,33 @@
 //      is one AES block under the hp key, expanded round by round in
 //      registers; the four lanes compute it redundantly (the same wave
 //      instructions as one lane would take, and no broadcast).
+//
+// The fused Salamander layer (template flag OB; the OB = false code is what it
+// was).  Key byte k covers packet byte k mod 32, so the period is aligned to
+// packet byte 0 and every offset below is the packet's, not the datagram's.
+//   keys<OB>:    the lane derives K from the keyring's PSK state (entry 0) and
+//      the packet's salt (open: the first 8 wire bytes; seal: salt[i])
+//      before HKDF, whose registers it then reuses; open XORs the 32 head
+//      bytes in registers (hd ^= K) and each varint byte past byte 32 with
+//      K[p & 31] as it is loaded.  K goes to the packet kernel through the
+//      workspace, in a 32-byte slot after the n records.
+//   protect<.., OB>: each lane holds K, and K rotated to the payload start
+//      (hdr & 31): payload block c takes half c & 1 of the rotated key,
+//      16-aligned header block b takes half b & 1 of K.  Open XORs on load
+//      (header blocks past byte 32, payload blocks, sample, tag) and then
+//      copies the datagram's remainder (coalesced packets), 64 bytes per quad
+//      step, de-obfuscated with K rotated to span & 31.  Seal hashes and
+//      samples the plain ciphertext and XORs only what it stores, the tag and
+//      the protected first byte and packet-number bytes included; quad lane 0
+//      writes the salt.  In place, open's output lies 8 bytes below its
+//      input: see the comments at the loads.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "sq_bytes.h"
 #include "sq_hash.h"
 #include "sq_internal.h"
+#include "sq_obfs_key.h"
 #include "sq_quic.h"
 #include "sq_quic_aes.h"
 #include "sq_quic_kdf.h"
@@ -62,10 +85,16 @@ constexpr uint32_t kMaxCid = 20;       // RFC 9000 17.2: v1 connection ids
 // The long header of a v1 Initial packet of len bytes at src (hd: its first
 // 32 bytes).  Returns 0, kQEHeader (not a well-formed Initial of this
 // version) or kQEShort (the header runs past len).  pno = the byte after the
-// Length field, length = that field.
+// Length field, length = that field.  OB: hd is de-obfuscated already, and a
+// byte past it is XORed with ok[its offset & 31] as it is loaded.
+template <bool OB>
 __device__ __forceinline__ uint32_t parse_initial(const uint32_t (&hd)[8], uint64_t src,
                                                   uint32_t len, uint32_t version, uint32_t &pno,
-                                                  uint64_t &length) {
+                                                  uint64_t &length, const uint32_t (&ok)[8]) {
+  auto hb = [&](uint32_t k) -> uint32_t {
+    const uint32_t b = head_byte(hd, src, k);
+    return (OB && k >= 32) ? b ^ byte32(ok, k & 31) : b;
+  };
   if ((hd[0] & 0xF0u) != 0xC0u) return kQEHeader;  // long form, fixed bit, type 00
   if (len < 7) return kQEShort;
   if (__builtin_bswap32(__builtin_amdgcn_alignbyte(hd[1], hd[0], 1)) != version) return kQEHeader;
@@ -82,13 +111,13 @@ __device__ __forceinline__ uint32_t parse_initial(const uint32_t (&hd)[8], uint6
       off_end = true;
       return 0;
     }
-    const uint32_t b0 = head_byte(hd, src, p), nb = 1u << (b0 >> 6);
+    const uint32_t b0 = hb(p), nb = 1u << (b0 >> 6);
     if (p + nb > len) {
       off_end = true;
       return 0;
     }
     uint64_t v = b0 & 0x3Fu;
-    for (uint32_t k = 1; k < nb; k++) v = (v << 8) | head_byte(hd, src, p + k);
+    for (uint32_t k = 1; k < nb; k++) v = (v << 8) | hb(p + k);
     p += nb;
     return v;
   };
@@ -125,20 +154,55 @@ __device__ __forceinline__ void hmac_block(const uint32_t (&im)[8], const uint32
   for (int i = 0; i < 12; i++) out[i] = i < 8 ? st[i & 7] : 0u;
 }
 
+// byte offset of packet i's Salamander key in the workspace of n packets
+__device__ __forceinline__ uint64_t okey_slot(const QInitParams &P, uint32_t i) {
+  return (uint64_t)(P.rec + P.n) + 32ull * i;
+}
+
+template <bool OB>
 __global__ __launch_bounds__(kIKBlock) void quic_initial_keys(const QInitParams P) {
   __shared__ uint32_t T[256];
   stage_t0<kIKBlock>(P.t0, T);
   const uint32_t i = blockIdx.x * kIKBlock + threadIdx.x;
   if (i >= P.n) return;
-  const uint64_t src = (uint64_t)P.in + P.in_off[i];
-  const uint32_t len = P.in_len[i];
+  uint64_t src = (uint64_t)P.in + P.in_off[i];
+  uint32_t len = P.in_len[i];
   const uint64_t rec = (uint64_t)(P.rec + i);
   uint32_t hd[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, pno = 0, span = 0;
+  uint32_t okey[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
   uint64_t length = 0;
+  if (OB) {  // the packet's Salamander key, before HKDF needs the registers
+    uint32_t osalt[4] = {0u, 0u, 0u, 0u};
+    if (!P.open) {
+      const u32x2 sv = gld<u32x2>((uint64_t)P.salt + 8ull * i);
+      osalt[0] = sv.x;
+      osalt[1] = sv.y;
+    } else if (len >= (uint32_t)kSalamanderSalt && len <= kQMaxPacket) {
+      load16(src, src + kSalamanderSalt, osalt);  // the first 8 wire bytes (salamander.go:50)
+      src += kSalamanderSalt;
+      len -= kSalamanderSalt;
+    } else {
+      len = 0;  // too short for a salt: rejected below
+    }
+    if (len) {
+      salamander_key(P.opsk, osalt, okey);
+      const uint64_t slot = okey_slot(P, i);
+      gst<u32x4>(slot, u32x4{okey[0], okey[1], okey[2], okey[3]});
+      gst<u32x4>(slot + 16, u32x4{okey[4], okey[5], okey[6], okey[7]});
+    }
+  }
   uint32_t err = len == 0 || len > kQMaxPacket ? kQEShort : 0u;
   if (!err) {
     load_head32(src, len, hd);
-    err = parse_initial(hd, src, len, P.version, pno, length);
+    if (OB) {  // open: the key period starts at packet byte 0; seal parses plain input
+      const uint32_t om = P.open ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        okey[j] &= om;
+        hd[j] ^= okey[j] & range_mask(0, (int)(len < 32 ? len : 32), j);
+      }
+    }
+    err = parse_initial<OB>(hd, src, len, P.version, pno, length, okey);
   }
   if (!err) {
     if (P.open) {  // the packet is [0, pno + Length): coalesced packets may follow
@@ -285,8 +349,26 @@ __device__ __forceinline__ uint32_t quad_xor(uint32_t v) {
   return v;
 }
 
+// w ^= half `odd` of the 32-byte key k (bytes 16 odd .. 16 odd + 15)
+__device__ __forceinline__ void xor_half(uint32_t (&w)[4], const uint32_t (&k)[8], bool odd) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) w[i] ^= bsel(odd, k[4 + i], k[i]);
+}
+
+// the 32-byte key k rotated left by r bytes: out byte i = k[(r + i) & 31]
+__device__ __forceinline__ void key_rot(const uint32_t (&k)[8], uint32_t r, uint32_t (&out)[8]) {
+  uint32_t a[4], b[4];
+  keywin(k, r, a);
+  keywin(k, r + 16, b);
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    out[i] = a[i];
+    out[4 + i] = b[i];
+  }
+}
+
 // One unit of a wave: packets [base, base + 16), packet slot q = lane / 4.
-template <bool OPEN>
+template <bool OPEN, bool OB>
 __device__ __forceinline__ void initial_unit(const QInitParams &P, uint64_t base, uint32_t lane,
                                              const uint32_t *tT, uint32_t tcol, IWave &W) {
   const uint32_t q = lane >> 2, j = lane & 3;
@@ -311,8 +393,23 @@ __device__ __forceinline__ void initial_unit(const QInitParams &P, uint64_t base
   const u32x4 h4v = gld<u32x4>(rec + offsetof(QInitRec, h) + 48);
   const u32x4 meta = gld<u32x4>(rec + offsetof(QInitRec, pn_offset));
   const uint32_t pno = meta.x, len = meta.y;  // len: the packet's bytes (open: its span)
-  const uint64_t src = (uint64_t)P.in + P.in_off[p], dst = (uint64_t)P.out + P.out_off[p];
+  // OB: the packet follows the 8 salt bytes of the wire datagram (open: in,
+  // seal: out); src, dst and every offset below are the packet's
+  const uint64_t wire = OPEN ? (uint64_t)P.in + P.in_off[p] : (uint64_t)P.out + P.out_off[p];
+  const uint64_t src = OB && OPEN ? wire + kSalamanderSalt : (uint64_t)P.in + P.in_off[p];
+  const uint64_t dst = OB && !OPEN ? wire + kSalamanderSalt : (uint64_t)P.out + P.out_off[p];
   const uint32_t hp[4] = {hpv.x, hpv.y, hpv.z, hpv.w}, iv[3] = {ive.x, ive.y, ive.z};
+  uint32_t ok[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // the packet's Salamander key
+  if (OB) {
+    const u32x4 a = gld<u32x4>(okey_slot(P, p)), b = gld<u32x4>(okey_slot(P, p) + 16);
+    ok[0] = a.x; ok[1] = a.y; ok[2] = a.z; ok[3] = a.w;
+    ok[4] = b.x; ok[5] = b.y; ok[6] = b.z; ok[7] = b.w;
+  }
+  // packet byte k as it is read (open: de-obfuscated)
+  auto hb = [&](const uint32_t (&h)[8], uint32_t k) -> uint32_t {
+    const uint32_t v = head_byte(h, src, k);
+    return (OB && OPEN && k >= 32) ? v ^ byte32(ok, k & 31) : v;
+  };
 
   // the quad's Shoup table of H^4: entry n = the nibble polynomial n times
   // H^4 (8 = H^4, 4 = H^4 x, 2 = H^4 x^2, 1 = H^4 x^3); lane j builds 4j..4j+3
@@ -339,18 +436,31 @@ __device__ __forceinline__ void initial_unit(const QInitParams &P, uint64_t base
 
   uint32_t hd[8];
   load_head32(src, len, hd);
+  if (OB && OPEN) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) hd[i] ^= ok[i] & range_mask(0, (int)(len < 32 ? len : 32), i);
+  }
   uint32_t first, pn_len, hdr, pl, pnb[4] = {0u, 0u, 0u, 0u}, rtag[4] = {0u, 0u, 0u, 0u};
   uint64_t pn = P.pn[p];
   if (OPEN) {  // header protection off, before any in-place write
     uint32_t sample[4], m0, m1;
     load16(src + pno + 4, src + len, sample);
     load16(src + len - 16, src + len, rtag);
+    if (OB) {  // (both are 16 whole bytes: pno + 4 + 16 <= len)
+      uint32_t kw[4];
+      keywin(ok, pno + 4, kw);
+#pragma unroll
+      for (int i = 0; i < 4; i++) sample[i] ^= kw[i];
+      keywin(ok, len - 16, kw);
+#pragma unroll
+      for (int i = 0; i < 4; i++) rtag[i] ^= kw[i];
+    }
     hp_mask_otf(tT, tcol, hp, sample, m0, m1);
     first = (hd[0] & 0xFFu) ^ (m0 & 0x0Fu);
     pn_len = (first & 3) + 1;
     uint64_t trunc = 0;
     for (uint32_t i = 0; i < pn_len; i++) {
-      pnb[i] = head_byte(hd, src, pno + i) ^ mask_byte(m0, m1, 1 + i);
+      pnb[i] = hb(hd, pno + i) ^ mask_byte(m0, m1, 1 + i);
       trunc = (trunc << 8) | pnb[i];
     }
     pn = decode_pn(pn, trunc, 8 * pn_len);
@@ -361,7 +471,7 @@ __device__ __forceinline__ void initial_unit(const QInitParams &P, uint64_t base
     pn_len = (first & 3) + 1;
     hdr = pno + pn_len;
     pl = len - hdr;
-    for (uint32_t i = 0; i < pn_len; i++) pnb[i] = head_byte(hd, src, pno + i);
+    for (uint32_t i = 0; i < pn_len; i++) pnb[i] = hb(hd, pno + i);
   }
   uint32_t nonce[3];
   quic_nonce_iv(iv, pn, nonce);
@@ -370,12 +480,41 @@ __device__ __forceinline__ void initial_unit(const QInitParams &P, uint64_t base
   const uint32_t A = (hdr + 15) / 16, C = (pl + 15) / 16, N = A + C + 1;
   const uint32_t *rk = W.rk[q], *tab = W.tab[q];
   uint32_t y[4] = {0u, 0u, 0u, 0u};
+  uint32_t okp[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // the key rotated to the payload start
+  if (OB) key_rot(ok, hdr, okp);
+  // OB open in place writes 8 bytes below where it reads.  Lanes of one step
+  // in the same branch below load (one instruction) before they store, and a
+  // header block's store ends below the next block's bytes.  But payload
+  // block 0 is stored over header bytes [hdr - 8, hdr), which lie in the last
+  // header block or the last two, and its branch may run before the header
+  // branch of the same step: so a lane loads here, ahead of every store, the
+  // one of those two blocks that is its own (hbl), when it comes from memory.
+  uint32_t hlast[4] = {0u, 0u, 0u, 0u};
+  const uint32_t hbl = A - 1 - ((A - 1 - j) & 3u);  // the lane's last header hblock
+  const bool pre = OB && OPEN && hbl + 2 >= A && hbl >= 2 && hbl < A;
+  if (pre) {
+    load16(src + 16 * hbl, src + hdr, hlast);
+    xor_half(hlast, ok, hbl & 1u);
+    const int nb = (int)(hdr - 16 * hbl);
+#pragma unroll
+    for (int i = 0; i < 4; i++) hlast[i] &= range_mask(0, nb, i);
+  }
   for (uint32_t b = j; b < N; b += 4) {
     if (b < A) {
       // the unprotected header, zero-padded; seal leaves it as it is
       // (protection is applied at the end), open writes it
       uint32_t w[4];
-      head_block(hd, src, 16 * b, hdr, w);
+      if (OB && OPEN && b >= 2) {  // from memory: de-obfuscated, zero past hdr
+        if (b + 2 >= A) {  // (b is hbl)
+#pragma unroll
+          for (int i = 0; i < 4; i++) w[i] = hlast[i];
+        } else {  // (a whole block)
+          load16(src + 16 * b, src + hdr, w);
+          xor_half(w, ok, b & 1u);
+        }
+      } else {
+        head_block(hd, src, 16 * b, hdr, w);
+      }
       if (OPEN) {
         if (b == 0) set_byte(w, 0, first);
         for (uint32_t i = 0; i < pn_len; i++) {
@@ -384,7 +523,8 @@ __device__ __forceinline__ void initial_unit(const QInitParams &P, uint64_t base
         }
       }
       ghash_absorb(y, w);
-      if (OPEN || dst != src) store16(dst + 16 * b, w, hdr - 16 * b < 16 ? hdr - 16 * b : 16);
+      if (OB && !OPEN) xor_half(w, ok, b & 1u);  // (store16 writes the header's bytes only)
+      if (OPEN || OB || dst != src) store16(dst + 16 * b, w, hdr - 16 * b < 16 ? hdr - 16 * b : 16);
     } else if (b < A + C) {
       // payload block c: counter 2 + c; every lane of the quad loads before
       // any of them stores (one wave), and each stores where it loaded
@@ -397,15 +537,22 @@ __device__ __forceinline__ void initial_unit(const QInitParams &P, uint64_t base
       } else {
         load16(S, S + nb, x);
       }
+      if (OB && OPEN) {  // block c of the payload: half c & 1 of the rotated key
+        xor_half(x, okp, c & 1u);
+#pragma unroll
+        for (int w = 0; w < 4; w++) x[w] &= nb == 16 ? 0xFFFFFFFFu : range_mask(0, (int)nb, w);
+      }
       aes_encrypt<0, 10>(rk, tT, tcol, ks);
       uint32_t ct[4];
 #pragma unroll
       for (int w = 0; w < 4; w++)
         ct[w] = (x[w] ^ ks[w]) & (nb == 16 ? 0xFFFFFFFFu : range_mask(0, (int)nb, w));
       ghash_absorb(y, OPEN ? x : ct);
+      // (seal: GHASH and the sample see the ciphertext, the wire its XOR)
+      if (!OPEN && c < 2) *(u32x4 *)&W.ct32[q][4 * c] = u32x4{ct[0], ct[1], ct[2], ct[3]};
+      if (OB && !OPEN) xor_half(ct, okp, c & 1u);
       if (nb == 16) gst<u32x4_a1>(D, u32x4_a1{ct[0], ct[1], ct[2], ct[3]});
       else store16(D, ct, nb);
-      if (!OPEN && c < 2) *(u32x4 *)&W.ct32[q][4 * c] = u32x4{ct[0], ct[1], ct[2], ct[3]};
     } else {  // be64(8 * hdr) || be64(8 * pl)
       y[1] ^= 8 * hdr;
       y[2] ^= pl >> 29;
@@ -427,13 +574,30 @@ __device__ __forceinline__ void initial_unit(const QInitParams &P, uint64_t base
 #pragma unroll
   for (int w = 0; w < 4; w++) tag[w] ^= __builtin_bswap32(y[w]);
   if (OPEN) {
+    const bool good = ((tag[0] ^ rtag[0]) | (tag[1] ^ rtag[1]) | (tag[2] ^ rtag[2]) |
+                       (tag[3] ^ rtag[3])) == 0;
+    if (OB && good) {
+      // the datagram's bytes after this packet (coalesced packets), to the
+      // offset they have in the packet: quad lane j takes bytes [64 s + 16 j,
+      // + 16) of them.  In place the stores of step s land 8 bytes below its
+      // loads: on the tag's bytes 8..15 (read into rtag above) and on bytes
+      // that the lane below loaded in the same instruction, or a step before
+      const uint32_t rem = P.in_len[p] - kSalamanderSalt - len;  // (the key kernel: >= 0)
+      uint32_t okt[8];
+      key_rot(ok, len, okt);
+      for (uint32_t o = 16 * j; o < rem; o += 64) {
+        const uint32_t nb = rem - o < 16 ? rem - o : 16;
+        uint32_t x[4];
+        load16(src + len + o, src + len + o + nb, x);
+        xor_half(x, okt, j & 1u);  // (o / 16 is j mod 4)
+        store16(dst + len + o, x, nb);
+      }
+    }
     if (j) return;
-    const bool ok = ((tag[0] ^ rtag[0]) | (tag[1] ^ rtag[1]) | (tag[2] ^ rtag[2]) |
-                     (tag[3] ^ rtag[3])) == 0;
-    P.out_len[p] = ok ? len - 16 : kQEAuth;
+    P.out_len[p] = good ? len - 16 : kQEAuth;
     if (P.pn_out) P.pn_out[p] = pn;
-    if (ok && P.pn_offset_out) P.pn_offset_out[p] = (uint16_t)pno;
-    if (ok && P.consumed) P.consumed[p] = len;
+    if (good && P.pn_offset_out) P.pn_offset_out[p] = (uint16_t)pno;
+    if (good && P.consumed) P.consumed[p] = len;
     return;
   }
   // header protection: sample = (ciphertext || tag)[4 - pn_len ..][0..16)
@@ -458,17 +622,27 @@ __device__ __forceinline__ void initial_unit(const QInitParams &P, uint64_t base
   }
   hp_mask_otf(tT, tcol, hp, sample, m0, m1);
   if (j) return;
+  if (OB) {
+    uint32_t kw[4];
+    keywin(ok, len, kw);
+#pragma unroll
+    for (int i = 0; i < 4; i++) tag[i] ^= kw[i];
+    const u32x2 sv = gld<u32x2>((uint64_t)P.salt + 8ull * p);
+    const uint32_t s4[4] = {sv.x, sv.y, 0u, 0u};
+    store16(wire, s4, kSalamanderSalt);
+  }
   store16(dst + len, tag, 16);
   // (the header blocks other lanes of the quad stored have landed)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  gst<uint8_t>(dst, (uint8_t)(first ^ (m0 & 0x0Fu)));
+  gst<uint8_t>(dst, (uint8_t)(first ^ (m0 & 0x0Fu) ^ (ok[0] & 0xFFu)));
   for (uint32_t i = 0; i < pn_len; i++)
-    gst<uint8_t>(dst + pno + i, (uint8_t)(pnb[i] ^ mask_byte(m0, m1, 1 + i)));
-  P.out_len[p] = len + 16;
+    gst<uint8_t>(dst + pno + i, (uint8_t)(pnb[i] ^ mask_byte(m0, m1, 1 + i) ^
+                                          (OB ? byte32(ok, (pno + i) & 31) : 0u)));
+  P.out_len[p] = len + 16 + (OB ? (uint32_t)kSalamanderSalt : 0u);
   if (P.pn_offset_out) P.pn_offset_out[p] = (uint16_t)pno;
 }
 
-template <bool OPEN>
+template <bool OPEN, bool OB>
 __global__ __launch_bounds__(kIBlock) void quic_initial_protect(const QInitParams P) {
   // the T-table image first (a lookup's row and column come from one v_perm,
   // the image's base is the immediate), then the waves' records
@@ -485,10 +659,10 @@ __global__ __launch_bounds__(kIBlock) void quic_initial_protect(const QInitParam
   const uint64_t units = ((uint64_t)P.n + kIPpw - 1) / kIPpw;
   const uint64_t stride = (uint64_t)gridDim.x * kIWaves;
   for (uint64_t u = (uint64_t)blockIdx.x * kIWaves + wv; u < units; u += stride)
-    initial_unit<OPEN>(P, u * kIPpw, lane, tT, tcol, waves[wv]);
+    initial_unit<OPEN, OB>(P, u * kIPpw, lane, tT, tcol, waves[wv]);
 }
 
-template <bool OPEN>
+template <bool OPEN, bool OB>
 static int launch_protect(const QInitParams *ip, hipStream_t s) {
   // the persistent grid: resident workgroups (queried once per instantiation)
   static const uint64_t cap = [] {
@@ -496,12 +670,12 @@ static int launch_protect(const QInitParams *ip, hipStream_t s) {
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, (const void *)quic_initial_protect<OPEN>, kIBlock, 0);
+        &per_cu, (const void *)quic_initial_protect<OPEN, OB>, kIBlock, 0);
     return (uint64_t)(per_cu < 1 ? 1 : per_cu) * (uint64_t)(cus < 1 ? 1 : cus);
   }();
   const uint64_t units = ((uint64_t)ip->n + kIPpw - 1) / kIPpw;
   const uint64_t want = (units + kIWaves - 1) / kIWaves;
-  hipLaunchKernelGGL((quic_initial_protect<OPEN>), dim3((uint32_t)(want < cap ? want : cap)),
+  hipLaunchKernelGGL((quic_initial_protect<OPEN, OB>), dim3((uint32_t)(want < cap ? want : cap)),
                      dim3(kIBlock), 0, s, *ip);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -513,8 +687,10 @@ extern "C" int sq_launch_quic_initial(const sq::QInitParams *ip, void *stream) {
   if (ip->n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();  // (a stale error is not this launch's: sq_kernels.hip launch_k)
-  hipLaunchKernelGGL(quic_initial_keys, dim3((ip->n + kIKBlock - 1) / kIKBlock), dim3(kIKBlock), 0,
-                     s, *ip);
+  const dim3 kgrid((ip->n + kIKBlock - 1) / kIKBlock);
+  if (ip->obfs) hipLaunchKernelGGL((quic_initial_keys<true>), kgrid, dim3(kIKBlock), 0, s, *ip);
+  else hipLaunchKernelGGL((quic_initial_keys<false>), kgrid, dim3(kIKBlock), 0, s, *ip);
   if (hipGetLastError() != hipSuccess) return -3;
-  return ip->open ? launch_protect<true>(ip, s) : launch_protect<false>(ip, s);
+  if (ip->obfs) return ip->open ? launch_protect<true, true>(ip, s) : launch_protect<false, true>(ip, s);
+  return ip->open ? launch_protect<true, false>(ip, s) : launch_protect<false, false>(ip, s);
 }

@@ -39,12 +39,18 @@
 //      header-protection mask (one ChaCha20 block, or one AES block under the
 //      entry's hp schedule with a plain LDS copy of the T-table) and writes
 //      the entry index with its low bit set to the packet's Key Phase bit.
+//      OB (sqobfs_quic_key_phase_salamander): the batch holds Hysteria2 wire
+//      datagrams, salt8 || packet ^ K.  The lane derives K = BLAKE2b-256(psk
+//      || salt) itself (the resolver runs before open, so no other kernel has
+//      made it yet) and de-obfuscates the two things it reads: the first
+//      byte with K[0], and the sample with K rotated to its packet offset.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "sq_bytes.h"
 #include "sq_hash.h"
 #include "sq_internal.h"
+#include "sq_obfs_key.h"
 #include "sq_quic.h"
 #include "sq_quic_kdf.h"
 #include "sqobfs.h"
@@ -228,7 +234,8 @@ static_assert(offsetof(QuicGcmKeyDev, hpos) % 16 == 0 && sizeof(QuicGcmKeyDev) %
 // ---------------------------------------------------------------- key phase
 
 // NR 0: ChaCha20 header protection; 10 / 14: AES-ECB under the entry's hrk
-template <int NR>
+// OB: the Salamander layer is still on (offsets are the packet's, after the salt)
+template <int NR, bool OB>
 __global__ __launch_bounds__(kPBlock) void quic_key_phase(const QPhaseParams P) {
   __shared__ uint32_t T[256];
   if (NR) stage_t0<kPBlock>(P.t0, T);
@@ -236,13 +243,27 @@ __global__ __launch_bounds__(kPBlock) void quic_key_phase(const QPhaseParams P) 
   if (i >= P.n) return;
   const uint32_t kid = P.key_id ? P.key_id[i] : 0u;
   uint32_t out = kid;
-  const uint32_t len = P.in_len[i], pno = P.pn_offset[i];
+  uint32_t len = P.in_len[i];
+  const uint32_t pno = P.pn_offset[i];
+  if (OB) len = len >= (uint32_t)kSalamanderSalt && len <= kQMaxPacket ? len - kSalamanderSalt : 0u;
   if (kid < P.n_keys && len >= 16 && len <= kQMaxPacket && pno + 4 + 16 <= len) {
-    const uint64_t src = (uint64_t)P.in + P.in_off[i];
-    const uint32_t first = gld<uint8_t>(src);
+    const uint64_t wire = (uint64_t)P.in + P.in_off[i], src = OB ? wire + kSalamanderSalt : wire;
+    uint32_t first = gld<uint8_t>(src), okey[8];
+    if (OB) {
+      uint32_t osalt[4];
+      load16(wire, wire + kSalamanderSalt, osalt);
+      salamander_key(&P.opsk, osalt, okey);
+      first ^= okey[0] & 0xFFu;
+    }
     if (!(first & 0x80u)) {  // short header: bit 0x04 is the Key Phase
       uint32_t s[4], mask0;
       load16(src + pno + 4, src + len, s);
+      if (OB) {  // key byte k covers packet byte k mod 32
+        uint32_t kw[4];
+        keywin(okey, pno + 4, kw);
+#pragma unroll
+        for (int k = 0; k < 4; k++) s[k] ^= kw[k];
+      }
       if (NR == 0) {
         uint32_t hp[8], o[16];
         const uint64_t a = (uint64_t)(P.keys + kid) + 44;
@@ -294,11 +315,19 @@ extern "C" int sq_launch_quic_key_phase(const sq::QPhaseParams *pp, void *stream
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((pp->n + kPBlock - 1) / kPBlock);
   (void)hipGetLastError();
-  if (pp->suite == SQOBFS_QUIC_CHACHA20_POLY1305)
-    hipLaunchKernelGGL((quic_key_phase<0>), grid, dim3(kPBlock), 0, s, *pp);
-  else if (pp->suite == SQOBFS_QUIC_AES_256_GCM)
-    hipLaunchKernelGGL((quic_key_phase<14>), grid, dim3(kPBlock), 0, s, *pp);
-  else
-    hipLaunchKernelGGL((quic_key_phase<10>), grid, dim3(kPBlock), 0, s, *pp);
+  const int nr = pp->suite == SQOBFS_QUIC_CHACHA20_POLY1305 ? 0
+                 : pp->suite == SQOBFS_QUIC_AES_256_GCM     ? 14
+                                                            : 10;
+#define SQ_PHASE(NR, OB) hipLaunchKernelGGL((quic_key_phase<NR, OB>), grid, dim3(kPBlock), 0, s, *pp)
+  if (pp->obfs) {
+    if (nr == 0) SQ_PHASE(0, true);
+    else if (nr == 14) SQ_PHASE(14, true);
+    else SQ_PHASE(10, true);
+  } else {
+    if (nr == 0) SQ_PHASE(0, false);
+    else if (nr == 14) SQ_PHASE(14, false);
+    else SQ_PHASE(10, false);
+  }
+#undef SQ_PHASE
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }

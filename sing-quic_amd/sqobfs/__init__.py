@@ -229,6 +229,11 @@ def load(path: str) -> ctypes.CDLL:
     L.sqobfs_quic_open.argtypes = [vp, vp, ctypes.POINTER(QuicBatch), vp]
     L.sqobfs_quic_seal_salamander.argtypes = [vp, vp, vp, ctypes.POINTER(QuicBatch), vp, vp]
     L.sqobfs_quic_open_salamander.argtypes = [vp, vp, vp, ctypes.POINTER(QuicBatch), vp]
+    L.sqobfs_quic_key_phase_salamander.argtypes = [vp, vp, vp, ctypes.POINTER(QuicBatch), vp, vp]
+    L.sqobfs_quic_initial_open_salamander.argtypes = [vp, vp, ctypes.POINTER(QuicBatch), u32, vp,
+                                                      vp, vp, vp, vp]
+    L.sqobfs_quic_initial_seal_salamander.argtypes = [vp, vp, ctypes.POINTER(QuicBatch), u32, vp,
+                                                      vp, vp, vp, vp]
     L.sqobfs_salt_key.argtypes = [vp, vp, ctypes.c_uint64]
     L.sqobfs_salt_seq.argtypes = [vp]
     L.sqobfs_salt_seq.restype = ctypes.c_uint64
@@ -938,3 +943,33 @@ def quic_open_salamander(ctx: Context, kr: QuicKeyring, okr: Keyring, batch: Qui
     _check(lib().sqobfs_quic_open_salamander(ctx.handle, kr.handle, okr.handle,
                                              ctypes.byref(batch), stream),
            "sqobfs_quic_open_salamander")
+
+
+def quic_key_phase_salamander(ctx: Context, kr: QuicKeyring, okr: Keyring, batch: QuicBatch,
+                              key_id_out, stream=None) -> None:
+    """quic_key_phase on wire datagrams of the fused path (batch as
+    quic_open_salamander takes it); key_id_out then feeds quic_open_salamander."""
+    _check(lib().sqobfs_quic_key_phase_salamander(ctx.handle, kr.handle, okr.handle,
+                                                  ctypes.byref(batch), _ptr(key_id_out), stream),
+           "sqobfs_quic_key_phase_salamander")
+
+
+def quic_initial_open_salamander(ctx: Context, okr: Keyring, batch: QuicBatch, side: int,
+                                 odcid=None, odcid_len=None, pn_offset_out=None, consumed=None,
+                                 stream=None) -> None:
+    """Salamander de-obfuscation + quic_initial_open in one pass: in = wire
+    datagrams; offsets are the QUIC packet's.  The datagram's bytes after an
+    opened packet land de-obfuscated at out[consumed:]."""
+    _check(lib().sqobfs_quic_initial_open_salamander(
+        ctx.handle, okr.handle, ctypes.byref(batch), side, _ptr(odcid), _ptr(odcid_len),
+        _ptr(pn_offset_out), _ptr(consumed), stream), "sqobfs_quic_initial_open_salamander")
+
+
+def quic_initial_seal_salamander(ctx: Context, okr: Keyring, batch: QuicBatch, side: int, salt,
+                                 odcid=None, odcid_len=None, pn_offset_out=None,
+                                 stream=None) -> None:
+    """quic_initial_seal + Salamander in one pass (wire = salt || obfs(packet),
+    one Initial per datagram); salt: device uint8 [n*8]."""
+    _check(lib().sqobfs_quic_initial_seal_salamander(
+        ctx.handle, okr.handle, ctypes.byref(batch), side, _ptr(odcid), _ptr(odcid_len),
+        _ptr(salt), _ptr(pn_offset_out), stream), "sqobfs_quic_initial_seal_salamander")
