@@ -579,6 +579,153 @@ int sqobfs_quic_initial_seal_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *o
                                         void *stream);
 
 /* ------------------------------------------------------------------------
+ * Routing received QUIC datagrams to their connections on the device.  New
+ * symbols and one new struct only: no struct above changes layout, so
+ * SQOBFS_ABI_VERSION stays as it is.
+ *
+ * Every call above takes key_id, pn_offset and pn per packet: the caller
+ * knows the connection.  A listener does not: one socket carries thousands
+ * of connections interleaved in each receive batch, new clients' Initials
+ * among them, and under Salamander not even the first byte is readable
+ * (quic-go looks each datagram up on the host: packet_handler_map.go,
+ * wire.ParseConnectionID).  Here a connection-id map lives on the device and
+ * one call classifies a ragged batch, finds each datagram's connection and
+ * writes the batch out partitioned by class in the array form the calls
+ * above take:  route -> key_phase -> open  (and initial_open for the Initial
+ * slice) run back to back on one stream, and the host reads 8 counters.
+ *
+ * The connection-id map.  cid_len (1..20) is the length of the connection
+ * ids this endpoint issues, one length per map, as quic-go uses; conns
+ * (1..32768) the connection slots, so that 2 * conn is a key id of a keyring
+ * made by sqobfs_quic_keyring_create_secrets; max_cids (>= 1) the most ids
+ * alive at once: several may map to one connection (NEW_CONNECTION_ID).
+ * Anything else: SQ_EINVAL.  The map is host-authoritative: the library
+ * keeps an open-addressing table (linear probing, a power of two >= 2 *
+ * max_cids of 32-byte slots) in host memory and an image of it on the
+ * device.  The map also owns pn_state[conns][3] on the device: the largest
+ * packet number received per connection in the Initial, Handshake and
+ * application spaces (RFC 9000 12.3), zero at creation. */
+typedef struct sqobfs_quic_cidmap sqobfs_quic_cidmap;
+typedef struct sqobfs_quic_cid_op {
+  uint8_t cid[20];  /* cid_len bytes are used */
+  uint32_t conn;    /* or SQOBFS_QUIC_CID_REMOVE */
+} sqobfs_quic_cid_op;
+#define SQOBFS_QUIC_CID_REMOVE 0xFFFFFFFFu
+#define SQOBFS_QUIC_NOCONN 0xFFFFFFFFu
+
+int sqobfs_quic_cidmap_create(sqobfs_ctx *ctx, uint32_t conns, uint32_t max_cids,
+                              uint32_t cid_len, sqobfs_quic_cidmap **out);
+void sqobfs_quic_cidmap_destroy(sqobfs_quic_cidmap *m);
+/* Applies ops[0..n) (host memory) in order: an insert maps the id to conn
+ * (an id already present gets the new conn), SQOBFS_QUIC_CID_REMOVE removes
+ * it (an absent id: no-op; removal shifts the probe chain back, there are
+ * no tombstones).  The changed table is then copied to the device on
+ * `stream` and the call returns when the copy has completed, as
+ * sqobfs_quic_keyring_rekey does; ordering it against launches that read the
+ * map is the caller's job, as there.  An update that would leave more than
+ * max_cids ids, or holds a conn >= conns that is not the REMOVE value,
+ * returns SQ_EINVAL and changes nothing. */
+int sqobfs_quic_cidmap_update(sqobfs_ctx *ctx, sqobfs_quic_cidmap *m, uint32_t n,
+                              const sqobfs_quic_cid_op *ops, void *stream);
+/* Connection slots conn[0..n) (host memory, each below conns, else
+ * SQ_EINVAL) are reused: their three packet numbers go back to 0.  Queued on
+ * `stream`; returns when it has completed. */
+int sqobfs_quic_cidmap_reset_pn(sqobfs_ctx *ctx, sqobfs_quic_cidmap *m, uint32_t n,
+                                const uint32_t *conn, void *stream);
+
+/* Classes of a routed datagram.  Only the first QUIC packet of a datagram is
+ * routed.  Under Salamander "the packet" is the datagram after its 8 salt
+ * bytes, XORed with BLAKE2b-256(psk || salt), key byte k & 31 on packet byte
+ * k; all offsets are the packet's.
+ *   SHORT      first byte 0x80 clear and 0x40 set, at least 1 + cid_len
+ *              bytes, the id at byte 1 is in the map
+ *   INITIAL    long header, fixed bit, version 1, type 00, dcid_len <= 20,
+ *              the header through the DCID inside the packet.  conn = the
+ *              map's answer when dcid_len == cid_len and the DCID is found,
+ *              else SQOBFS_QUIC_NOCONN (a new client)
+ *   HANDSHAKE  long, fixed bit, version 1, type 10; dcid_len == cid_len and
+ *              found; scid_len <= 20; the Length varint (any encoding)
+ *              parsed: pn_offset = the byte after it, and the packet's span
+ *              pn_offset + Length lies inside the packet
+ *   ZERO_RTT   as HANDSHAKE with type 01
+ *   OTHER      a long header with version != 1 (version negotiation, v2,
+ *              others), or a v1 Retry (type 11)
+ *   UNKNOWN    shaped as SHORT, HANDSHAKE or ZERO_RTT, but the id is not in
+ *              the map or the long header's dcid_len != cid_len (stray
+ *              packets, stateless-reset candidates)
+ *   MALFORMED  an empty packet (under Salamander: a datagram of fewer than 9
+ *              bytes); a short header with the fixed bit clear or shorter
+ *              than 1 + cid_len; a long header cut before its version ends;
+ *              a v1 long header with the fixed bit clear, a connection-id
+ *              length above 20, or a header or span that runs off the end */
+#define SQOBFS_QUIC_ROUTE_SHORT 0u
+#define SQOBFS_QUIC_ROUTE_INITIAL 1u
+#define SQOBFS_QUIC_ROUTE_HANDSHAKE 2u
+#define SQOBFS_QUIC_ROUTE_ZERO_RTT 3u
+#define SQOBFS_QUIC_ROUTE_OTHER 4u
+#define SQOBFS_QUIC_ROUTE_UNKNOWN 5u
+#define SQOBFS_QUIC_ROUTE_MALFORMED 6u
+
+/* What a routing call writes (device pointers, all required but out_off).
+ * Class k occupies [count[0] + .. + count[k - 1], + count[k]) of every
+ * partitioned array, input order kept within a class.  Per class:
+ *              SHORT         HANDSHAKE / ZERO_RTT     INITIAL       others
+ *   in_len     datagram's    the span (+ 8 under      datagram's    datagram's
+ *                            Salamander: a prefix
+ *                            of the wire datagram)
+ *   pn_offset  1 + cid_len   parsed                   0             0
+ *   key_id     2 * conn      2 * conn                 0             0
+ *   pn         pn_state      Handshake: [conn][1]     [conn][0], 0  0
+ *              [conn][2]     0-RTT: [conn][2]         with NOCONN
+ * in_off and out_off are the datagram's own in every class. */
+typedef struct sqobfs_quic_routed {
+  uint8_t *cls;        /* [n] class per datagram, input order */
+  uint32_t *count;     /* [8] datagrams per class (entry 7 = 0) */
+  uint32_t *order;     /* [n] index of the datagram in the input batch */
+  uint64_t *in_off;    /* [n] */
+  uint32_t *in_len;    /* [n] */
+  uint64_t *out_off;   /* [n], or NULL when b->out_off is NULL */
+  uint16_t *pn_offset; /* [n] */
+  uint64_t *pn;        /* [n] */
+  uint16_t *key_id;    /* [n] */
+  uint32_t *conn;      /* [n] connection or SQOBFS_QUIC_NOCONN */
+} sqobfs_quic_routed;
+
+/* Routes the batch: b supplies n, in, in_off, in_len and optionally out_off
+ * (the rest of b is not read); b->pn_offset, b->pn and b->key_id must be
+ * NULL, because they are what the call produces.  The input is not modified.
+ * sqobfs_quic_route_salamander takes wire datagrams; okr as
+ * sqobfs_quic_key_phase_salamander takes it.  The caller reads count (32
+ * bytes) and points a sqobfs_quic_batch at a slice: SHORT, HANDSHAKE and
+ * ZERO_RTT slices go to sqobfs_quic_key_phase and sqobfs_quic_open (or the
+ * _salamander forms; the caller's Handshake keyring uses the same 2 * conn
+ * convention), INITIAL to sqobfs_quic_initial_open(_salamander) with b->pn
+ * the slice of pn.  Coalesced remainders are routed by a second
+ * sqobfs_quic_route at in_off + consumed: always the plain form, since the
+ * fused Initial open leaves the remainder de-obfuscated.  Three kernels are
+ * queued on `stream` (NULL: the HIP null stream); the call does not wait.
+ * SQ_EINVAL before anything is launched: a NULL argument or required
+ * pointer, b->flags, b->pn_offset / pn / key_id not NULL, r->out_off without
+ * b->out_off, a map of another context, okr NULL, not a Salamander keyring
+ * or of another context. */
+int sqobfs_quic_route(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m, const sqobfs_quic_batch *b,
+                      const sqobfs_quic_routed *r, void *stream);
+int sqobfs_quic_route_salamander(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
+                                 const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
+                                 const sqobfs_quic_routed *r, void *stream);
+
+/* After a slice was opened: for every j in [0, n) with conn[j] !=
+ * SQOBFS_QUIC_NOCONN and out_len[j] not a SQOBFS_QUIC_E* code,
+ *   pn_state[conn[j]][space] = max(pn_state[conn[j]][space], pn_out[j])
+ * (space: 0 Initial, 1 Handshake, 2 application; conn, out_len and pn_out
+ * are device arrays, e.g. the slice of r->conn and open's outputs).  Queued
+ * on `stream`, no wait: the next batch's route on the same stream decodes
+ * against what this batch authenticated.  space > 2: SQ_EINVAL. */
+int sqobfs_quic_cidmap_commit(sqobfs_ctx *ctx, sqobfs_quic_cidmap *m, uint32_t space, uint32_t n,
+                              const uint32_t *conn, const uint32_t *out_len,
+                              const uint64_t *pn_out, void *stream);
+
+/* ------------------------------------------------------------------------
  * Several GPUs in one process (packets are independent, so a
  * batch shards into contiguous ranges with no exchange at all).
  */

@@ -58,6 +58,9 @@ struct sqobfs_ctx {
   // kernels of a call share them), and the device AES T-table
   std::unordered_map<hipStream_t, std::pair<void *, uint64_t>> init_ws;
   uint32_t *init_t0 = nullptr;
+  // datagram routing (sq_quic_route.hip): the records and workgroup counts
+  // that its three kernels share, cached and guarded as init_ws is
+  std::unordered_map<hipStream_t, std::pair<void *, uint64_t>> route_ws;
 };
 
 namespace {
@@ -295,6 +298,11 @@ void sq_ctx_stream_destroy(sqobfs_ctx *ctx, void *s) {
     if (iw != ctx->init_ws.end()) {
       tab_free(iw->second.first);
       ctx->init_ws.erase(iw);
+    }
+    auto ir = ctx->route_ws.find((hipStream_t)s);
+    if (ir != ctx->route_ws.end()) {
+      tab_free(ir->second.first);
+      ctx->route_ws.erase(ir);
     }
   }
   (void)hipStreamDestroy((hipStream_t)s);
@@ -752,6 +760,8 @@ void sqobfs_close(sqobfs_ctx *ctx) {
   for (auto &kv : ctx->gcm_scratch)
     tab_free(kv.second.first);
   for (auto &kv : ctx->init_ws)
+    tab_free(kv.second.first);
+  for (auto &kv : ctx->route_ws)
     tab_free(kv.second.first);
   tab_free(ctx->init_t0);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1836,6 +1846,293 @@ int sqobfs_quic_initial_seal_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *o
   if (!okr) return SQ_EINVAL;
   return quic_initial_launch(0, ctx, b, side, odcid, odcid_len, pn_offset_out, nullptr, stream,
                              okr, salt);
+}
+
+// ---- routing received datagrams: the connection-id map and the route call
+extern "C++" {
+// Host-authoritative: `host` is the table (linear probing, a slot with conn ==
+// kQuicNoConn is empty, removal by backward shift), `dev` its image.  Slots
+// [dirty_lo, dirty_hi) differ from the image until cid_flush copies them.
+struct sqobfs_quic_cidmap {
+  sqobfs_ctx *ctx = nullptr;
+  mutable KeyringUses uses;
+  uint32_t conns = 0, max_cids = 0, cid_len = 0, mask = 0, live = 0;
+  std::vector<sq::CidSlot> host;
+  uint32_t dirty_lo = 0, dirty_hi = 0;
+  sq::CidSlot *dev = nullptr;
+  uint64_t *pn_state = nullptr;  // device [conns][3]
+};
+
+namespace {
+struct CidKey {
+  uint32_t w[sq::kCidWords];
+};
+
+CidKey cid_key(const uint8_t *cid, uint32_t len) {
+  uint8_t b[4 * sq::kCidWords] = {0};
+  memcpy(b, cid, len);
+  CidKey k;
+  for (uint32_t j = 0; j < sq::kCidWords; j++) k.w[j] = le32(b + 4 * j);
+  return k;
+}
+
+void cid_touch(sqobfs_quic_cidmap *m, uint32_t s) {
+  if (m->dirty_lo == m->dirty_hi) {
+    m->dirty_lo = s;
+    m->dirty_hi = s + 1;
+  } else {
+    m->dirty_lo = std::min(m->dirty_lo, s);
+    m->dirty_hi = std::max(m->dirty_hi, s + 1);
+  }
+}
+
+// the key's slot, or the empty slot that ends its probe chain
+uint32_t cid_find(const sqobfs_quic_cidmap *m, const CidKey &k) {
+  uint32_t s = sq::cid_hash(k.w) & m->mask;
+  while (m->host[s].conn != sq::kQuicNoConn && memcmp(m->host[s].cid, k.w, sizeof k.w) != 0)
+    s = (s + 1) & m->mask;
+  return s;
+}
+
+// Maps the key to conn (kQuicNoConn: removes it) and returns what it was
+// mapped to before (kQuicNoConn: absent).
+uint32_t cid_set(sqobfs_quic_cidmap *m, const CidKey &k, uint32_t conn) {
+  uint32_t i = cid_find(m, k);
+  const uint32_t prev = m->host[i].conn;
+  if (conn != sq::kQuicNoConn) {
+    memcpy(m->host[i].cid, k.w, sizeof k.w);
+    m->host[i].conn = conn;
+    m->live += prev == sq::kQuicNoConn;
+    cid_touch(m, i);
+    return prev;
+  }
+  if (prev == sq::kQuicNoConn) return prev;
+  // backward shift: a later entry of the chain moves into the hole unless
+  // its home slot lies (cyclically) after the hole
+  for (uint32_t j = i;;) {
+    j = (j + 1) & m->mask;
+    if (m->host[j].conn == sq::kQuicNoConn) break;
+    const uint32_t home = sq::cid_hash(m->host[j].cid) & m->mask;
+    if (i <= j ? (i < home && home <= j) : (i < home || home <= j)) continue;
+    m->host[i] = m->host[j];
+    cid_touch(m, i);
+    i = j;
+  }
+  memset(&m->host[i], 0, sizeof m->host[i]);
+  m->host[i].conn = sq::kQuicNoConn;
+  cid_touch(m, i);
+  m->live--;
+  return prev;
+}
+
+// the slots that changed -> the device image, waited for
+int cid_flush(sqobfs_quic_cidmap *m, hipStream_t s) {
+  if (m->dirty_lo == m->dirty_hi) return SQ_OK;
+  hipError_t e = hipMemcpyAsync(m->dev + m->dirty_lo, m->host.data() + m->dirty_lo,
+                                sizeof(sq::CidSlot) * (m->dirty_hi - m->dirty_lo),
+                                hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) m->dirty_lo = m->dirty_hi = 0;
+  return hip_status(e);
+}
+}  // namespace
+}  // extern "C++"
+
+int sqobfs_quic_cidmap_create(sqobfs_ctx *ctx, uint32_t conns, uint32_t max_cids, uint32_t cid_len,
+                              sqobfs_quic_cidmap **out) {
+  if (out) *out = nullptr;
+  if (!ctx || !out || conns == 0 || conns > sq::kQuicMaxConns || max_cids == 0 ||
+      max_cids > (1u << 30) || cid_len == 0 || cid_len > 4 * sq::kCidWords)
+    return SQ_EINVAL;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  sqobfs_quic_cidmap *m = new (std::nothrow) sqobfs_quic_cidmap();
+  if (!m) return SQ_ENOMEM;
+  m->ctx = ctx;
+  m->conns = conns;
+  m->max_cids = max_cids;
+  m->cid_len = cid_len;
+  uint32_t slots = 4;  // (an update holds max_cids + 1 ids before it is refused: never full)
+  while (slots < 2 * max_cids) slots *= 2;
+  m->mask = slots - 1;
+  sq::CidSlot empty;
+  memset(&empty, 0, sizeof empty);
+  empty.conn = sq::kQuicNoConn;
+  m->host.assign(slots, empty);
+  m->dirty_hi = slots;  // the whole image, once
+  hipStream_t s = ctx->stream;
+  const size_t pbytes = sizeof(uint64_t) * 3 * conns;
+  hipError_t e = tab_alloc((void **)&m->dev, sizeof(sq::CidSlot) * slots, s);
+  if (e == hipSuccess) e = tab_alloc((void **)&m->pn_state, pbytes, s);
+  if (e == hipSuccess) e = hipMemsetAsync(m->pn_state, 0, pbytes, s);
+  int st = hip_status(e);
+  if (st == SQ_OK) st = cid_flush(m, s);
+  if (st != SQ_OK) {
+    (void)hipStreamSynchronize(s);
+    tab_free_async(m->dev, s);
+    tab_free_async(m->pn_state, s);
+    (void)hipStreamSynchronize(s);
+    delete m;
+    return st;
+  }
+  *out = m;
+  return SQ_OK;
+}
+
+void sqobfs_quic_cidmap_destroy(sqobfs_quic_cidmap *m) {
+  if (!m) return;
+  DeviceScope ds_(m->ctx->device);
+  m->uses.fence(m->ctx->rel);  // as sqobfs_keyring_destroy: stream-ordered, no wait
+  tab_free_async(m->dev, m->ctx->rel);
+  tab_free_async(m->pn_state, m->ctx->rel);
+  delete m;
+}
+
+int sqobfs_quic_cidmap_update(sqobfs_ctx *ctx, sqobfs_quic_cidmap *m, uint32_t n,
+                              const sqobfs_quic_cid_op *ops, void *stream) {
+  if (!ctx || !m || m->ctx != ctx) return SQ_EINVAL;
+  if (n == 0) return SQ_OK;
+  if (!ops) return SQ_EINVAL;
+  for (uint32_t i = 0; i < n; i++)
+    if (ops[i].conn >= m->conns && ops[i].conn != SQOBFS_QUIC_CID_REMOVE) return SQ_EINVAL;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  // in order, remembering what each id was mapped to: an update that
+  // overflows is taken back op by op (the ids' slots may then differ from
+  // before, their connections do not)
+  std::vector<uint32_t> prev(n);
+  uint32_t done = 0;
+  for (; done < n; done++) {
+    prev[done] = cid_set(m, cid_key(ops[done].cid, m->cid_len), ops[done].conn);
+    if (m->live > m->max_cids) break;
+  }
+  const bool overflow = done < n;
+  if (overflow)
+    for (uint32_t i = done + 1; i-- > 0;) (void)cid_set(m, cid_key(ops[i].cid, m->cid_len), prev[i]);
+  const int st = cid_flush(m, pick_stream(ctx, stream));
+  return overflow ? SQ_EINVAL : st;
+}
+
+int sqobfs_quic_cidmap_reset_pn(sqobfs_ctx *ctx, sqobfs_quic_cidmap *m, uint32_t n,
+                                const uint32_t *conn, void *stream) {
+  if (!ctx || !m || m->ctx != ctx) return SQ_EINVAL;
+  if (n == 0) return SQ_OK;
+  if (!conn) return SQ_EINVAL;
+  for (uint32_t i = 0; i < n; i++)
+    if (conn[i] >= m->conns) return SQ_EINVAL;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  hipStream_t s = pick_stream(ctx, stream);
+  uint32_t *args = nullptr;
+  hipError_t e = tab_alloc((void **)&args, sizeof(uint32_t) * n, s);
+  if (e != hipSuccess) return hip_status(e);
+  int st = hip_status(hipMemcpyAsync(args, conn, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+  if (st == SQ_OK) st = sq_launch_quic_pn_reset(m->pn_state, m->conns, n, args, s);
+  tab_free_async(args, s);
+  const int sy = hip_status(hipStreamSynchronize(s));
+  return st == SQ_OK ? sy : st;
+}
+
+int sqobfs_quic_cidmap_commit(sqobfs_ctx *ctx, sqobfs_quic_cidmap *m, uint32_t space, uint32_t n,
+                              const uint32_t *conn, const uint32_t *out_len,
+                              const uint64_t *pn_out, void *stream) {
+  if (!ctx || !m || m->ctx != ctx || space > 2) return SQ_EINVAL;
+  if (n == 0) return SQ_OK;
+  if (!conn || !out_len || !pn_out) return SQ_EINVAL;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  hipStream_t s = pick_stream(ctx, stream);
+  const int st = sq_launch_quic_pn_commit(m->pn_state, m->conns, space, n, conn, out_len, pn_out, s);
+  if (st == SQ_OK) m->uses.note(s);
+  return st;
+}
+
+static int quic_route_launch(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
+                             const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
+                             const sqobfs_quic_routed *r, void *stream) {
+  if (!ctx || !m || m->ctx != ctx || !b || b->flags || !r || !r->count) return SQ_EINVAL;
+  if (okr && (okr->ctx != ctx || okr->kind != SQOBFS_SALAMANDER)) return SQ_EINVAL;
+  if (b->pn_offset || b->pn || b->key_id || (r->out_off && !b->out_off)) return SQ_EINVAL;
+  if (b->n && (!b->in || !b->in_off || !b->in_len || !r->cls || !r->order || !r->in_off ||
+               !r->in_len || !r->pn_offset || !r->pn || !r->key_id || !r->conn))
+    return SQ_EINVAL;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  sq::QRouteParams rp;
+  memset(&rp, 0, sizeof rp);
+  rp.in = b->in;
+  rp.in_off = b->in_off;
+  rp.in_len = b->in_len;
+  rp.out_off = b->out_off;
+  rp.slots = m->dev;
+  rp.pn_state = m->pn_state;
+  rp.r_cls = r->cls;
+  rp.r_count = r->count;
+  rp.r_order = r->order;
+  rp.r_in_off = r->in_off;
+  rp.r_in_len = r->in_len;
+  rp.r_out_off = r->out_off;
+  rp.r_pn_offset = r->pn_offset;
+  rp.r_pn = r->pn;
+  rp.r_key_id = r->key_id;
+  rp.r_conn = r->conn;
+  rp.n = b->n;
+  rp.nwg = (uint32_t)(((uint64_t)b->n + sq::kRouteBlock - 1) / sq::kRouteBlock);
+  rp.slot_mask = m->mask;
+  rp.cid_len = m->cid_len;
+  if (okr) {  // entry 0 of the keyring's device table, as the Initial key kernel reads it
+    rp.obfs = 1;
+    rp.opsk = okr->table;
+  }
+  hipStream_t s = pick_stream(ctx, stream);
+  // held over the three launches: two threads on one stream share its workspace
+  std::lock_guard<std::mutex> lk(ctx->gcm_mu);
+  // records [n][4] | numbers [n] | workgroup counts [nwg][8] | class bases [8]:
+  // cached per library-owned stream, else this call's own (as the Initial records)
+  const uint64_t rec_b = 16ull * b->n, pn_b = 8ull * b->n, wg_b = 32ull * rp.nwg;
+  const uint64_t bytes = rec_b + pn_b + wg_b + 32;
+  void *ws = nullptr;
+  const bool cached = s == ctx->stream || ctx->gcm_scratch.count(s);
+  if (cached) {
+    auto &e = ctx->route_ws[s];
+    if (e.second < bytes) {
+      const uint64_t want = std::max<uint64_t>(bytes, 2 * e.second);
+      tab_free_async(e.first, s);
+      e = {nullptr, 0};
+      if (tab_alloc(&e.first, want, s) == hipSuccess) e.second = want;
+      else e.first = nullptr;
+    }
+    ws = e.first;
+  } else if (tab_alloc(&ws, bytes, s) != hipSuccess) {
+    ws = nullptr;
+  }
+  if (!ws) {
+    (void)hipGetLastError();
+    return SQ_ENOMEM;
+  }
+  rp.ws_rec = (uint32_t *)ws;
+  rp.ws_pn = (uint64_t *)((uint8_t *)ws + rec_b);
+  rp.ws_wg = (uint32_t *)((uint8_t *)ws + rec_b + pn_b);
+  rp.ws_base = (uint32_t *)((uint8_t *)ws + rec_b + pn_b + wg_b);
+  const int st = sq_launch_quic_route(&rp, s);
+  if (!cached) tab_free_async(ws, s);
+  if (st == SQ_OK) {
+    m->uses.note(s);
+    if (okr) okr->uses.note(s);
+  }
+  return st;
+}
+
+int sqobfs_quic_route(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m, const sqobfs_quic_batch *b,
+                      const sqobfs_quic_routed *r, void *stream) {
+  return quic_route_launch(ctx, m, nullptr, b, r, stream);
+}
+
+int sqobfs_quic_route_salamander(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
+                                 const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
+                                 const sqobfs_quic_routed *r, void *stream) {
+  if (!okr) return SQ_EINVAL;
+  return quic_route_launch(ctx, m, okr, b, r, stream);
 }
 
 size_t sqobfs_host_staging_bytes(const sqobfs_ctx *ctx) { return ctx ? ctx->pinned_cap : 0; }

@@ -261,7 +261,80 @@ struct QInitParams {
   const PskEntry *opsk;
 };
 
+// Connection-ID routing (sq_quic_route.hip).  One slot of the open-addressing
+// table that the host keeps (sq_api.hip) and the device probes: the CID
+// zero-padded to 20 bytes as little-endian words, then its connection.  32
+// bytes, so a lane reads a slot with two 16-byte loads.
+#ifdef __HIPCC__
+#define SQ_HD __host__ __device__
+#else
+#define SQ_HD
+#endif
+constexpr uint32_t kQuicNoConn = 0xFFFFFFFFu;  // SQOBFS_QUIC_NOCONN; in a slot: empty
+constexpr uint32_t kCidWords = 5;              // RFC 9000 17.2: at most 20 bytes
+constexpr uint32_t kRouteClasses = 7;          // SQOBFS_QUIC_ROUTE_* (count[7] stays 0)
+struct alignas(16) CidSlot {
+  uint32_t cid[kCidWords];
+  uint32_t conn;
+  uint32_t pad[2];
+};
+static_assert(sizeof(CidSlot) == 32, "CidSlot layout");
+// The table's hash, the same on both sides (fixed seed: the endpoint issues
+// its own connection ids).  A multiply carries each word's bits upwards and
+// the shift brings them back down to the bits that pick the slot.
+SQ_HD inline uint32_t cid_hash(const uint32_t (&c)[kCidWords]) {
+  uint32_t h = 0x9E3779B9u;
+  for (uint32_t j = 0; j < kCidWords; j++) {
+    h = (h ^ c[j]) * 0x85EBCA6Bu;
+    h ^= h >> 15;
+  }
+  h *= 0xC2B2AE35u;
+  return h ^ (h >> 16);
+}
+
+// One routing call: three launches (classify, scan, scatter).  ws_*: the
+// call's workspace; r_*: sqobfs_quic_routed.
+struct QRouteParams {
+  const uint8_t *in;
+  const uint64_t *in_off;
+  const uint32_t *in_len;
+  const uint64_t *out_off;   // or NULL
+  const CidSlot *slots;      // [slot_mask + 1]
+  const uint64_t *pn_state;  // [conns][3]: initial, handshake, application
+  const PskEntry *opsk;      // fused: the Salamander keyring's device entry 0
+  uint32_t *ws_rec;          // [n][4] conn | in_len out | pn_offset + (class << 16) | 0
+  uint64_t *ws_pn;           // [n]
+  uint32_t *ws_wg;           // [nwg][8] per workgroup: class counts, then class bases
+  uint32_t *ws_base;         // [8] first index of each class
+  uint8_t *r_cls;
+  uint32_t *r_count;
+  uint32_t *r_order;
+  uint64_t *r_in_off;
+  uint32_t *r_in_len;
+  uint64_t *r_out_off;       // or NULL
+  uint16_t *r_pn_offset;
+  uint64_t *r_pn;
+  uint16_t *r_key_id;
+  uint32_t *r_conn;
+  uint32_t n;
+  uint32_t nwg;
+  uint32_t slot_mask;
+  uint32_t cid_len;
+  uint32_t obfs;
+};
+constexpr uint32_t kRouteBlock = 256;  // datagrams per workgroup (sq_api.hip sizes ws_wg by it)
+
 }  // namespace sq
+
+// launchers implemented in sq_quic_route.hip.  pn_commit: pn_state[conn[j]]
+// [space] = max(.., pn_out[j]) for opened packets; pn_reset: a connection's
+// three numbers back to 0
+extern "C" int sq_launch_quic_route(const sq::QRouteParams *rp, void *stream);
+extern "C" int sq_launch_quic_pn_commit(uint64_t *pn_state, uint32_t conns, uint32_t space,
+                                        uint32_t n, const uint32_t *conn, const uint32_t *out_len,
+                                        const uint64_t *pn_out, void *stream);
+extern "C" int sq_launch_quic_pn_reset(uint64_t *pn_state, uint32_t conns, uint32_t n,
+                                       const uint32_t *conn, void *stream);
 
 // launcher implemented in sq_quic_initial.hip: both kernels on `stream`
 extern "C" int sq_launch_quic_initial(const sq::QInitParams *ip, void *stream);

@@ -127,6 +127,21 @@ QUIC_EKEY, QUIC_ESHORT, QUIC_EAUTH = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD
 QUIC_CHACHA20_POLY1305, QUIC_AES_128_GCM, QUIC_AES_256_GCM = 0, 1, 2  # SQOBFS_QUIC_* suites
 QUIC_EHEADER = 0xFFFFFFFC  # Initial packets: not a well-formed v1 Initial
 QUIC_SIDE_CLIENT, QUIC_SIDE_SERVER = 0, 1  # whose Initial keys protect the packets
+# classes of a routed datagram (SQOBFS_QUIC_ROUTE_*)
+(QUIC_ROUTE_SHORT, QUIC_ROUTE_INITIAL, QUIC_ROUTE_HANDSHAKE, QUIC_ROUTE_ZERO_RTT, QUIC_ROUTE_OTHER,
+ QUIC_ROUTE_UNKNOWN, QUIC_ROUTE_MALFORMED) = range(7)
+QUIC_NOCONN = QUIC_CID_REMOVE = 0xFFFFFFFF
+
+
+class QuicCidOp(ctypes.Structure):
+    """sqobfs_quic_cid_op: map the connection id to conn, or remove it."""
+    _fields_ = [("cid", ctypes.c_uint8 * 20), ("conn", ctypes.c_uint32)]
+
+
+class QuicRoutedPtrs(ctypes.Structure):
+    """sqobfs_quic_routed."""
+    _fields_ = [(f, ctypes.c_void_p) for f in ("cls", "count", "order", "in_off", "in_len",
+                                               "out_off", "pn_offset", "pn", "key_id", "conn")]
 
 
 class UdpView(ctypes.Structure):
@@ -234,6 +249,17 @@ def load(path: str) -> ctypes.CDLL:
                                                       vp, vp, vp, vp]
     L.sqobfs_quic_initial_seal_salamander.argtypes = [vp, vp, ctypes.POINTER(QuicBatch), u32, vp,
                                                       vp, vp, vp, vp]
+    if hasattr(L, "sqobfs_quic_route"):  # (absent from earlier builds)
+        L.sqobfs_quic_cidmap_create.argtypes = [vp, u32, u32, u32, ctypes.POINTER(vp)]
+        L.sqobfs_quic_cidmap_destroy.argtypes = [vp]
+        L.sqobfs_quic_cidmap_destroy.restype = None
+        L.sqobfs_quic_cidmap_update.argtypes = [vp, vp, u32, vp, vp]
+        L.sqobfs_quic_cidmap_reset_pn.argtypes = [vp, vp, u32, vp, vp]
+        L.sqobfs_quic_cidmap_commit.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+        L.sqobfs_quic_route.argtypes = [vp, vp, ctypes.POINTER(QuicBatch),
+                                        ctypes.POINTER(QuicRoutedPtrs), vp]
+        L.sqobfs_quic_route_salamander.argtypes = [vp, vp, vp, ctypes.POINTER(QuicBatch),
+                                                   ctypes.POINTER(QuicRoutedPtrs), vp]
     L.sqobfs_salt_key.argtypes = [vp, vp, ctypes.c_uint64]
     L.sqobfs_salt_seq.argtypes = [vp]
     L.sqobfs_salt_seq.restype = ctypes.c_uint64
@@ -973,3 +999,105 @@ def quic_initial_seal_salamander(ctx: Context, okr: Keyring, batch: QuicBatch, s
     _check(lib().sqobfs_quic_initial_seal_salamander(
         ctx.handle, okr.handle, ctypes.byref(batch), side, _ptr(odcid), _ptr(odcid_len),
         _ptr(salt), _ptr(pn_offset_out), stream), "sqobfs_quic_initial_seal_salamander")
+
+
+# ---------------------------------------------------------------- QUIC routing
+
+class QuicCidMap:
+    """The connection-id map of a listener on the device (sqobfs_quic_cidmap):
+    connection ids of cid_len bytes -> connection slots below conns, and each
+    connection's largest received packet number per space."""
+
+    def __init__(self, ctx: Context, conns: int, max_cids: int, cid_len: int):
+        h = ctypes.c_void_p()
+        _check(lib().sqobfs_quic_cidmap_create(ctx.handle, conns, max_cids, cid_len,
+                                               ctypes.byref(h)), "sqobfs_quic_cidmap_create")
+        self.handle, self.ctx, self.cid_len = h, ctx, cid_len
+
+    def update(self, ops: list[tuple[bytes, int]], stream=None) -> None:
+        """ops in order: (cid, conn) maps the id, (cid, QUIC_CID_REMOVE) removes
+        it.  Returns when the device copy is in place."""
+        arr = (QuicCidOp * max(len(ops), 1))()
+        for a, (cid, conn) in zip(arr, ops):
+            assert len(cid) == self.cid_len
+            ctypes.memmove(a.cid, cid, len(cid))
+            a.conn = conn
+        _check(lib().sqobfs_quic_cidmap_update(self.ctx.handle, self.handle, len(ops), arr,
+                                               stream), "sqobfs_quic_cidmap_update")
+
+    def reset_pn(self, conns: list[int], stream=None) -> None:
+        """The connection slots are reused: their packet numbers restart at 0."""
+        idx = (ctypes.c_uint32 * max(len(conns), 1))(*conns)
+        _check(lib().sqobfs_quic_cidmap_reset_pn(self.ctx.handle, self.handle, len(conns), idx,
+                                                 stream), "sqobfs_quic_cidmap_reset_pn")
+
+    def commit(self, space: int, n: int, conn, out_len, pn_out, stream=None) -> None:
+        """Raise the connections' largest packet numbers of `space` (0 Initial,
+        1 Handshake, 2 application) to the opened packets' (device arrays of n)."""
+        _check(lib().sqobfs_quic_cidmap_commit(self.ctx.handle, self.handle, space, n, _ptr(conn),
+                                               _ptr(out_len), _ptr(pn_out), stream),
+               "sqobfs_quic_cidmap_commit")
+
+    def close(self) -> None:
+        if self.handle:
+            lib().sqobfs_quic_cidmap_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class QuicRouted:
+    """The outputs of a routing call (sqobfs_quic_routed) as torch tensors on
+    `device`; out_off only when the routed batch has one."""
+    FIELDS = (("cls", np.uint8), ("count", np.uint32), ("order", np.uint32),
+              ("in_off", np.uint64), ("in_len", np.uint32), ("out_off", np.uint64),
+              ("pn_offset", np.uint16), ("pn", np.uint64), ("key_id", np.uint16),
+              ("conn", np.uint32))
+
+    def __init__(self, n: int, device, out_off: bool = True):
+        import torch
+        self.n = n
+        for name, dt in self.FIELDS:
+            size = 8 if name == "count" else max(n, 1)
+            t = torch.from_numpy(np.zeros(size, dt)).to(device)
+            setattr(self, name, t if out_off or name != "out_off" else None)
+
+    def ptrs(self) -> QuicRoutedPtrs:
+        return QuicRoutedPtrs(*[_ptr(getattr(self, name)) for name, _ in self.FIELDS])
+
+    def counts(self) -> list[int]:
+        """count[0..8) on the host: all the host reads between route and open."""
+        return self.count.cpu().numpy().tolist()
+
+    def batch(self, cls: int, counts: list[int], in_, out, out_len, pn_out=None) -> QuicBatch:
+        """Class cls's slice as the batch the open calls take (out_len, pn_out:
+        device arrays of counts[cls]); an Initial slice has no pn_offset / key_id."""
+        lo, hi = sum(counts[:cls]), sum(counts[:cls + 1])
+        cut = lambda t: None if t is None else t[lo:hi]  # noqa: E731
+        keyed = cls != QUIC_ROUTE_INITIAL
+        return quic_batch(hi - lo, in_, cut(self.in_off), cut(self.in_len), out, cut(self.out_off),
+                          out_len, cut(self.pn_offset) if keyed else None, cut(self.pn),
+                          cut(self.key_id) if keyed else None, pn_out)
+
+
+def quic_route(ctx: Context, cmap: QuicCidMap, batch: QuicBatch, routed: QuicRouted,
+               stream=None) -> None:
+    """Classify the batch's datagrams, find their connections and write the
+    batch partitioned by class into `routed` (batch: in, in_off, in_len and
+    optionally out_off; pn_offset, pn and key_id None)."""
+    p = routed.ptrs()
+    _check(lib().sqobfs_quic_route(ctx.handle, cmap.handle, ctypes.byref(batch), ctypes.byref(p),
+                                   stream), "sqobfs_quic_route")
+
+
+def quic_route_salamander(ctx: Context, cmap: QuicCidMap, okr: Keyring, batch: QuicBatch,
+                          routed: QuicRouted, stream=None) -> None:
+    """quic_route on Hysteria2 wire datagrams (salt first, Salamander still on)."""
+    p = routed.ptrs()
+    _check(lib().sqobfs_quic_route_salamander(ctx.handle, cmap.handle, okr.handle,
+                                              ctypes.byref(batch), ctypes.byref(p), stream),
+           "sqobfs_quic_route_salamander")
