@@ -726,6 +726,92 @@ int sqobfs_quic_cidmap_commit(sqobfs_ctx *ctx, sqobfs_quic_cidmap *m, uint32_t s
                               const uint64_t *pn_out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Address validation: Retry packets and their tokens on the device (RFC 9000
+ * 8.1.2, 17.2.5; RFC 9001 5.8).  New symbols only: no struct above changes
+ * layout, so SQOBFS_ABI_VERSION stays as it is.
+ *
+ * A route call's INITIAL slice with conn == SQOBFS_QUIC_NOCONN holds new
+ * clients, probes and, under attack, spoofed floods; opening an Initial costs
+ * a key derivation and GCM over the whole datagram.  The chain is
+ *   route -> retry_check -> OK: initial_open (odcid_out for the transport
+ *                               parameters);  NONE: retry -> send
+ * (partitioning by status is the caller's job).  A Retry is about 100 bytes
+ * and stateless; all packets of a call share the endpoint's token key and the
+ * fixed Retry integrity key.
+ *
+ * The Retry built for Initial I (i-th datagram):
+ *   0xF0 | 00000001 | scid_len(I) scid(I) | rscid_len rscid[i] | token | tag16
+ * tag = AES-128-GCM(the RFC 9001 5.8 key and nonce, empty plaintext, AAD =
+ * dcid_len(I) dcid(I) || the Retry without its tag).
+ *
+ * Tokens made by the library (53 bytes, the project's own format, opaque to
+ * clients):  nonce12 || C || T,  (C, T) = AES-128-GCM(tkr entry 0's key,
+ * IV = entry 0's iv XOR nonce12, AAD, P) with
+ *   P   (25) = issued_at (u32 big-endian, = now) || odcid_len || odcid zero-
+ *              padded to 20; odcid = the Initial's DCID
+ *   AAD (39) = addr[i] (18) || cid_len || cid zero-padded to 20; cid =
+ *              rscid[i] when building; when checking, the DCID of the Initial
+ *              that carries the token (a client answers a Retry with DCID =
+ *              the Retry's SCID): the token is tied to address and id. */
+#define SQOBFS_QUIC_RETRY_TOKEN_LEN 53u /* tokens made by the library */
+#define SQOBFS_QUIC_RETRY_TOKEN_MAX 64u /* tokens given by the caller */
+#define SQOBFS_QUIC_RETRY_MAX 127u      /* longest Retry packet (add 8 on the wire under Salamander) */
+
+typedef struct sqobfs_quic_retry_args {
+  const sqobfs_quic_keyring *tkr; /* AES-128-GCM keyring; entry 0's key and iv protect tokens (hp unused) */
+  const uint8_t *addr;      /* [n*18] device: client address, 16 bytes (v4 mapped) + port, opaque to the library */
+  const uint8_t *nonce;     /* [n*12] device: unique per token under one key (retry only) */
+  const uint8_t *rscid;     /* [n*20] device: the Retry's Source Connection ID (retry only) */
+  uint32_t rscid_len;       /* 1..20, one per call (the map's cid_len) (retry only) */
+  uint32_t now;             /* seconds, the caller's clock */
+  uint32_t max_age;         /* check only */
+  const uint8_t *token;     /* optional [n*64] device: caller's own tokens, used verbatim ... */
+  const uint8_t *token_len; /* ... [n], each 1..64 (more counts as 64); then tkr / addr / nonce /
+                               now are not read (retry only) */
+} sqobfs_quic_retry_args;
+
+/* status[i] of sqobfs_quic_retry_check */
+#define SQOBFS_QUIC_TOKEN_NONE 0u    /* token length 0 */
+#define SQOBFS_QUIC_TOKEN_OK 1u
+#define SQOBFS_QUIC_TOKEN_FOREIGN 2u /* length != 53 (e.g. a NEW_TOKEN token): the host decides */
+#define SQOBFS_QUIC_TOKEN_BAD 3u     /* tag mismatch */
+#define SQOBFS_QUIC_TOKEN_EXPIRED 4u /* (uint32_t)(now - issued_at) > max_age: also the future */
+#define SQOBFS_QUIC_TOKEN_EHEADER 5u /* not a well-formed v1 Initial */
+
+/* b supplies n, in, in_off, in_len and, retry, out, out_off, out_len (each
+ * packet SQOBFS_QUIC_RETRY_MAX bytes of room, + 8 under Salamander; out
+ * disjoint from in); b->pn_offset, pn, key_id, pn_out and flags must be NULL /
+ * 0.  The input is not modified.  One kernel is queued on `stream`; the
+ * calls do not wait.
+ *   retry: the input must parse as a v1 Initial, by sqobfs_quic_initial_open's
+ *     header checks and codes (out_len[i] = SQOBFS_QUIC_EHEADER / _ESHORT,
+ *     nothing written); span and payload are not examined.  Else out_len[i] =
+ *     the Retry's length.  _salamander: in holds wire datagrams, out gets
+ *     salt[i] || packet ^ BLAKE2b-256(psk || salt[i]), 8 bytes more.
+ *   retry_check: status[i] as above (a bad header: TOKEN_EHEADER); the
+ *     token-length varint in any encoding; odcid_out[20 i ..] (zero-padded),
+ *     odcid_len_out[i] and issued_at_out[i] (optional) are written for OK
+ *     and EXPIRED only.
+ * SQ_EINVAL before anything is launched: a NULL argument or required pointer;
+ * tkr (when it is read) not an AES-128-GCM keyring or of another context;
+ * exactly one of token / token_len; retry: rscid_len outside 1..20, salt
+ * NULL; okr as sqobfs_quic_route_salamander refuses it. */
+int sqobfs_quic_retry(sqobfs_ctx *ctx, const sqobfs_quic_batch *b,
+                      const sqobfs_quic_retry_args *a, void *stream);
+int sqobfs_quic_retry_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                                 const sqobfs_quic_batch *b, const sqobfs_quic_retry_args *a,
+                                 const uint8_t *salt /* [n*8] device */, void *stream);
+int sqobfs_quic_retry_check(sqobfs_ctx *ctx, const sqobfs_quic_batch *b,
+                            const sqobfs_quic_retry_args *a, uint8_t *status,
+                            uint8_t *odcid_out /* [n*20] */, uint8_t *odcid_len_out,
+                            uint32_t *issued_at_out /* optional */, void *stream);
+int sqobfs_quic_retry_check_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                                       const sqobfs_quic_batch *b,
+                                       const sqobfs_quic_retry_args *a, uint8_t *status,
+                                       uint8_t *odcid_out, uint8_t *odcid_len_out,
+                                       uint32_t *issued_at_out, void *stream);
+
+/* ------------------------------------------------------------------------
  * Several GPUs in one process (packets are independent, so a
  * batch shards into contiguous ranges with no exchange at all).
  */

@@ -61,6 +61,10 @@ struct sqobfs_ctx {
   // datagram routing (sq_quic_route.hip): the records and workgroup counts
   // that its three kernels share, cached and guarded as init_ws is
   std::unordered_map<hipStream_t, std::pair<void *, uint64_t>> route_ws;
+  // Retry packets (sq_quic_retry.hip): the AES T-table (256 words), then the
+  // 4-bit table of the Retry integrity key's H (64 words); made at the first
+  // call, guarded by gcm_mu
+  uint32_t *retry_consts = nullptr;
 };
 
 namespace {
@@ -764,6 +768,7 @@ void sqobfs_close(sqobfs_ctx *ctx) {
   for (auto &kv : ctx->route_ws)
     tab_free(kv.second.first);
   tab_free(ctx->init_t0);
+  tab_free(ctx->retry_consts);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->dev) (void)hipFree(ctx->dev);
   (void)hipStreamDestroy(ctx->stream);
@@ -2133,6 +2138,152 @@ int sqobfs_quic_route_salamander(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
                                  const sqobfs_quic_routed *r, void *stream) {
   if (!okr) return SQ_EINVAL;
   return quic_route_launch(ctx, m, okr, b, r, stream);
+}
+
+// ---- Retry packets and their tokens (sq_quic_retry.hip)
+extern "C++" {
+namespace {
+// What the kernel needs of RFC 9001 5.8's fixed AES-128-GCM key and nonce:
+// the 4-bit table of its H (the position table of the last nibble is n H) and
+// E_K(J0); the Retry's plaintext is empty, so its tag is GHASH ^ E_K(J0).
+struct RetryConsts {
+  uint32_t tab[64];
+  uint32_t ekj0[4];
+};
+const RetryConsts &retry_v1() {
+  static const RetryConsts c = [] {
+    static const uint8_t key[16] = {0xbe, 0x0c, 0x69, 0x0b, 0x9f, 0x66, 0x57, 0x5a,
+                                    0x1d, 0x76, 0x6b, 0x54, 0xe3, 0x68, 0xc8, 0x4e};
+    static const uint8_t j0[16] = {0x46, 0x15, 0x99, 0xd3, 0x5d, 0x63, 0x2b, 0xf2,
+                                   0x23, 0x98, 0x25, 0xbb, 0, 0, 0, 1};
+    RetryConsts r;
+    sqobfs_quic_key k;
+    memset(&k, 0, sizeof k);
+    memcpy(k.key, key, sizeof key);
+    std::vector<sq::QuicGcmKeyDev> d(1);
+    gcm_key(SQOBFS_QUIC_AES_128_GCM, k, d[0]);
+    memcpy(r.tab, d[0].hpos[31], sizeof r.tab);
+    uint32_t rk[44];
+    uint8_t e[16];
+    aes128_expand(key, rk);
+    aes_block(rk, 10, j0, e);
+    for (int i = 0; i < 4; i++) r.ekj0[i] = le32(e + 4 * i);
+    return r;
+  }();
+  return c;
+}
+
+int quic_retry_launch(int check, sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                      const sqobfs_quic_batch *b, const sqobfs_quic_retry_args *a,
+                      const uint8_t *salt, uint8_t *status, uint8_t *odcid_out,
+                      uint8_t *odcid_len_out, uint32_t *issued_at_out, void *stream) {
+  if (!ctx || !b || !a || b->flags || b->pn_offset || b->pn || b->key_id || b->pn_out)
+    return SQ_EINVAL;
+  if (okr && (okr->ctx != ctx || okr->kind != SQOBFS_SALAMANDER || (!check && !salt)))
+    return SQ_EINVAL;
+  if ((a->token == nullptr) != (a->token_len == nullptr)) return SQ_EINVAL;
+  const bool own = !check && a->token;  // the caller's tokens: the token key is not read
+  if (!own && (!a->tkr || a->tkr->ctx != ctx || a->tkr->suite != SQOBFS_QUIC_AES_128_GCM ||
+               !a->addr || (!check && !a->nonce)))
+    return SQ_EINVAL;
+  if (!check && (!a->rscid || a->rscid_len < 1 || a->rscid_len > 20)) return SQ_EINVAL;
+  if (!b->in || !b->in_off || !b->in_len) return SQ_EINVAL;
+  if (check ? !status || !odcid_out || !odcid_len_out : !b->out || !b->out_off || !b->out_len)
+    return SQ_EINVAL;
+  if (b->n == 0) return SQ_OK;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  const RetryConsts &c = retry_v1();
+  sq::QRetryParams rp;
+  memset(&rp, 0, sizeof rp);
+  rp.in = b->in;
+  rp.in_off = b->in_off;
+  rp.in_len = b->in_len;
+  rp.addr = a->addr;
+  rp.n = b->n;
+  rp.now = a->now;
+  if (check) {
+    rp.max_age = a->max_age;
+    rp.status = status;
+    rp.odcid_out = odcid_out;
+    rp.odcid_len_out = odcid_len_out;
+    rp.issued_at_out = issued_at_out;
+  } else {
+    rp.out = b->out;
+    rp.out_off = b->out_off;
+    rp.out_len = b->out_len;
+    rp.nonce = a->nonce;
+    rp.rscid = a->rscid;
+    rp.rscid_len = a->rscid_len;
+    rp.token = a->token;
+    rp.token_len = a->token_len;
+    rp.salt = salt;
+  }
+  if (!own) {  // entry 0: its schedule and iv by value, its table of H on the device
+    memcpy(rp.trk, a->tkr->grk0, sizeof rp.trk);
+    memcpy(rp.tiv, a->tkr->giv0, sizeof rp.tiv);
+    rp.htok = &a->tkr->gtable[0].hpos[31][0][0];
+  }
+  memcpy(rp.ekj0, c.ekj0, sizeof rp.ekj0);
+  if (okr) rp.opsk = okr->table;
+  hipStream_t s = pick_stream(ctx, stream);
+  {
+    std::lock_guard<std::mutex> lk(ctx->gcm_mu);
+    if (!ctx->retry_consts) {  // once per context; waited for, as any stream may use it next
+      uint32_t *p = nullptr;
+      hipError_t e = tab_alloc((void **)&p, sizeof(uint32_t) * (256 + 64), s);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(p, aes_tables().t0, sizeof(uint32_t) * 256, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(p + 256, c.tab, sizeof c.tab, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      if (e != hipSuccess) {
+        tab_free_async(p, s);
+        return hip_status(e);
+      }
+      ctx->retry_consts = p;
+    }
+  }
+  rp.t0 = ctx->retry_consts;
+  rp.rtab = ctx->retry_consts + 256;
+  const int st = sq_launch_quic_retry(check, okr != nullptr, &rp, s);
+  if (st == SQ_OK) {
+    if (!own) a->tkr->uses.note(s);
+    if (okr) okr->uses.note(s);
+  }
+  return st;
+}
+}  // namespace
+}  // extern "C++"
+
+int sqobfs_quic_retry(sqobfs_ctx *ctx, const sqobfs_quic_batch *b,
+                      const sqobfs_quic_retry_args *a, void *stream) {
+  return quic_retry_launch(0, ctx, nullptr, b, a, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           stream);
+}
+
+int sqobfs_quic_retry_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                                 const sqobfs_quic_batch *b, const sqobfs_quic_retry_args *a,
+                                 const uint8_t *salt, void *stream) {
+  if (!okr || !salt) return SQ_EINVAL;
+  return quic_retry_launch(0, ctx, okr, b, a, salt, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+int sqobfs_quic_retry_check(sqobfs_ctx *ctx, const sqobfs_quic_batch *b,
+                            const sqobfs_quic_retry_args *a, uint8_t *status, uint8_t *odcid_out,
+                            uint8_t *odcid_len_out, uint32_t *issued_at_out, void *stream) {
+  return quic_retry_launch(1, ctx, nullptr, b, a, nullptr, status, odcid_out, odcid_len_out,
+                           issued_at_out, stream);
+}
+
+int sqobfs_quic_retry_check_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                                       const sqobfs_quic_batch *b,
+                                       const sqobfs_quic_retry_args *a, uint8_t *status,
+                                       uint8_t *odcid_out, uint8_t *odcid_len_out,
+                                       uint32_t *issued_at_out, void *stream) {
+  if (!okr) return SQ_EINVAL;
+  return quic_retry_launch(1, ctx, okr, b, a, nullptr, status, odcid_out, odcid_len_out,
+                           issued_at_out, stream);
 }
 
 size_t sqobfs_host_staging_bytes(const sqobfs_ctx *ctx) { return ctx ? ctx->pinned_cap : 0; }

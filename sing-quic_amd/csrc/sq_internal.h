@@ -324,7 +324,45 @@ struct QRouteParams {
 };
 constexpr uint32_t kRouteBlock = 256;  // datagrams per workgroup (sq_api.hip sizes ws_wg by it)
 
+// Retry packets and their address-validation tokens (sq_quic_retry.hip): one
+// launch.  Every datagram uses the same two keys: the endpoint's token key
+// (trk, tiv, and htok = the 4-bit table of its H in the keyring's device
+// entry) and RFC 9001 5.8's fixed Retry integrity key, of which only the
+// table of H (rtab) and E_K(J0) (ekj0) are needed: its plaintext is empty.
+struct QRetryParams {
+  const uint8_t *in;
+  const uint64_t *in_off;
+  const uint32_t *in_len;
+  uint8_t *out;              // retry
+  const uint64_t *out_off;
+  uint32_t *out_len;
+  const uint8_t *addr;       // [n * 18]
+  const uint8_t *nonce;      // [n * 12] retry
+  const uint8_t *rscid;      // [n * 20] retry
+  const uint8_t *token;      // [n * 64] retry: the caller's tokens, or NULL
+  const uint8_t *token_len;  // [n]
+  const uint8_t *salt;       // [n * 8] fused retry: the Retry datagrams' salts
+  uint8_t *status;           // check
+  uint8_t *odcid_out;        // [n * 20]
+  uint8_t *odcid_len_out;    // [n]
+  uint32_t *issued_at_out;   // [n] or NULL
+  const uint32_t *t0;        // AES T-table (256 words)
+  const uint32_t *htok;      // [16][4] n H of the token key, or NULL (caller's tokens)
+  const uint32_t *rtab;      // [16][4] n H of the Retry integrity key
+  const PskEntry *opsk;      // fused: the Salamander keyring's device entry 0
+  uint32_t n;
+  uint32_t rscid_len;
+  uint32_t now;
+  uint32_t max_age;
+  uint32_t trk[44];          // token key schedule, as QuicGcmKeyDev::rk
+  uint32_t tiv[3];
+  uint32_t ekj0[4];          // E_K(J0) of the Retry integrity key, little-endian words
+};
+
 }  // namespace sq
+
+// launcher implemented in sq_quic_retry.hip: quic_retry<check, obfs>
+extern "C" int sq_launch_quic_retry(int check, int obfs, const sq::QRetryParams *rp, void *stream);
 
 // launchers implemented in sq_quic_route.hip.  pn_commit: pn_state[conn[j]]
 // [space] = max(.., pn_out[j]) for opened packets; pn_reset: a connection's

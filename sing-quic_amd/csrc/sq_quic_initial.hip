@@ -73,63 +73,10 @@
 
 namespace sq {
 
-constexpr uint32_t kQEHeader = 0xFFFFFFFCu;  // SQOBFS_QUIC_EHEADER
 constexpr uint32_t kIKBlock = 64;   // keys: one wave per workgroup (spreads small batches)
 constexpr uint32_t kIBlock = 768;   // protect: 12 waves, one workgroup per CU
 constexpr uint32_t kIWaves = kIBlock / kWave;
 constexpr uint32_t kIPpw = kWave / 4;  // packets per wave: one per quad
-constexpr uint32_t kMaxCid = 20;       // RFC 9000 17.2: v1 connection ids
-
-// ---------------------------------------------------------------- header
-
-// The long header of a v1 Initial packet of len bytes at src (hd: its first
-// 32 bytes).  Returns 0, kQEHeader (not a well-formed Initial of this
-// version) or kQEShort (the header runs past len).  pno = the byte after the
-// Length field, length = that field.  OB: hd is de-obfuscated already, and a
-// byte past it is XORed with ok[its offset & 31] as it is loaded.
-template <bool OB>
-__device__ __forceinline__ uint32_t parse_initial(const uint32_t (&hd)[8], uint64_t src,
-                                                  uint32_t len, uint32_t version, uint32_t &pno,
-                                                  uint64_t &length, const uint32_t (&ok)[8]) {
-  auto hb = [&](uint32_t k) -> uint32_t {
-    const uint32_t b = head_byte(hd, src, k);
-    return (OB && k >= 32) ? b ^ byte32(ok, k & 31) : b;
-  };
-  if ((hd[0] & 0xF0u) != 0xC0u) return kQEHeader;  // long form, fixed bit, type 00
-  if (len < 7) return kQEShort;
-  if (__builtin_bswap32(__builtin_amdgcn_alignbyte(hd[1], hd[0], 1)) != version) return kQEHeader;
-  const uint32_t dl = (hd[1] >> 8) & 0xFFu;  // byte 5
-  if (dl > kMaxCid) return kQEHeader;
-  if (6 + dl >= len) return kQEShort;
-  const uint32_t sl = byte32(hd, 6 + dl);  // (at most byte 26)
-  if (sl > kMaxCid) return kQEHeader;
-  uint32_t p = 7 + dl + sl;
-  bool off_end = false;
-  // RFC 9000 16: the first byte's two high bits give the length (1, 2, 4, 8)
-  auto varint = [&]() -> uint64_t {
-    if (p >= len) {
-      off_end = true;
-      return 0;
-    }
-    const uint32_t b0 = hb(p), nb = 1u << (b0 >> 6);
-    if (p + nb > len) {
-      off_end = true;
-      return 0;
-    }
-    uint64_t v = b0 & 0x3Fu;
-    for (uint32_t k = 1; k < nb; k++) v = (v << 8) | hb(p + k);
-    p += nb;
-    return v;
-  };
-  const uint64_t tok = varint();
-  if (off_end || tok > len - p) return kQEShort;
-  p += (uint32_t)tok;
-  length = varint();
-  if (off_end) return kQEShort;
-  if (p > 0xFFFFu) return kQEHeader;  // (pn_offset_out holds 16 bits)
-  pno = p;
-  return 0;
-}
 
 // ---------------------------------------------------------------- keys
 

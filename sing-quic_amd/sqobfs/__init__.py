@@ -131,6 +131,10 @@ QUIC_SIDE_CLIENT, QUIC_SIDE_SERVER = 0, 1  # whose Initial keys protect the pack
 (QUIC_ROUTE_SHORT, QUIC_ROUTE_INITIAL, QUIC_ROUTE_HANDSHAKE, QUIC_ROUTE_ZERO_RTT, QUIC_ROUTE_OTHER,
  QUIC_ROUTE_UNKNOWN, QUIC_ROUTE_MALFORMED) = range(7)
 QUIC_NOCONN = QUIC_CID_REMOVE = 0xFFFFFFFF
+# Retry packets and their tokens (SQOBFS_QUIC_RETRY_*, SQOBFS_QUIC_TOKEN_*)
+QUIC_RETRY_TOKEN_LEN, QUIC_RETRY_TOKEN_MAX, QUIC_RETRY_MAX = 53, 64, 127
+(QUIC_TOKEN_NONE, QUIC_TOKEN_OK, QUIC_TOKEN_FOREIGN, QUIC_TOKEN_BAD, QUIC_TOKEN_EXPIRED,
+ QUIC_TOKEN_EHEADER) = range(6)
 
 
 class QuicCidOp(ctypes.Structure):
@@ -142,6 +146,14 @@ class QuicRoutedPtrs(ctypes.Structure):
     """sqobfs_quic_routed."""
     _fields_ = [(f, ctypes.c_void_p) for f in ("cls", "count", "order", "in_off", "in_len",
                                                "out_off", "pn_offset", "pn", "key_id", "conn")]
+
+
+class QuicRetryArgs(ctypes.Structure):
+    """sqobfs_quic_retry_args."""
+    _fields_ = [("tkr", ctypes.c_void_p), ("addr", ctypes.c_void_p), ("nonce", ctypes.c_void_p),
+                ("rscid", ctypes.c_void_p), ("rscid_len", ctypes.c_uint32),
+                ("now", ctypes.c_uint32), ("max_age", ctypes.c_uint32),
+                ("token", ctypes.c_void_p), ("token_len", ctypes.c_void_p)]
 
 
 class UdpView(ctypes.Structure):
@@ -260,6 +272,12 @@ def load(path: str) -> ctypes.CDLL:
                                         ctypes.POINTER(QuicRoutedPtrs), vp]
         L.sqobfs_quic_route_salamander.argtypes = [vp, vp, vp, ctypes.POINTER(QuicBatch),
                                                    ctypes.POINTER(QuicRoutedPtrs), vp]
+    if hasattr(L, "sqobfs_quic_retry"):  # (absent from earlier builds)
+        qb, ra = ctypes.POINTER(QuicBatch), ctypes.POINTER(QuicRetryArgs)
+        L.sqobfs_quic_retry.argtypes = [vp, qb, ra, vp]
+        L.sqobfs_quic_retry_salamander.argtypes = [vp, vp, qb, ra, vp, vp]
+        L.sqobfs_quic_retry_check.argtypes = [vp, qb, ra, vp, vp, vp, vp, vp]
+        L.sqobfs_quic_retry_check_salamander.argtypes = [vp, vp, qb, ra, vp, vp, vp, vp, vp]
     L.sqobfs_salt_key.argtypes = [vp, vp, ctypes.c_uint64]
     L.sqobfs_salt_seq.argtypes = [vp]
     L.sqobfs_salt_seq.restype = ctypes.c_uint64
@@ -1101,3 +1119,46 @@ def quic_route_salamander(ctx: Context, cmap: QuicCidMap, okr: Keyring, batch: Q
     _check(lib().sqobfs_quic_route_salamander(ctx.handle, cmap.handle, okr.handle,
                                               ctypes.byref(batch), ctypes.byref(p), stream),
            "sqobfs_quic_route_salamander")
+
+
+def quic_retry_args(tkr: QuicKeyring | None = None, addr=None, nonce=None, rscid=None,
+                    rscid_len: int = 0, now: int = 0, max_age: int = 0, token=None,
+                    token_len=None) -> QuicRetryArgs:
+    """sqobfs_quic_retry_args over device uint8 tensors: addr [n*18], nonce
+    [n*12], rscid [n*20]; token [n*64] and token_len [n] for the caller's own
+    tokens (then tkr, addr, nonce and now are not read)."""
+    a = QuicRetryArgs(tkr.handle if tkr is not None else None, _ptr(addr), _ptr(nonce),
+                      _ptr(rscid), rscid_len, now, max_age, _ptr(token), _ptr(token_len))
+    a._keep = (tkr, addr, nonce, rscid, token, token_len)
+    return a
+
+
+def quic_retry(ctx: Context, batch: QuicBatch, args: QuicRetryArgs, okr: Keyring | None = None,
+               salt=None, stream=None) -> None:
+    """Build a Retry packet for every v1 Initial of the batch (out_len: its
+    length, or QUIC_EHEADER / QUIC_ESHORT).  okr: the batch holds Hysteria2
+    wire datagrams and the Retries leave as salt[i] || packet ^ key (salt:
+    device uint8 [n*8])."""
+    if okr is None:
+        _check(lib().sqobfs_quic_retry(ctx.handle, ctypes.byref(batch), ctypes.byref(args), stream),
+               "sqobfs_quic_retry")
+    else:
+        _check(lib().sqobfs_quic_retry_salamander(ctx.handle, okr.handle, ctypes.byref(batch),
+                                                  ctypes.byref(args), _ptr(salt), stream),
+               "sqobfs_quic_retry_salamander")
+
+
+def quic_retry_check(ctx: Context, batch: QuicBatch, args: QuicRetryArgs, status, odcid_out,
+                     odcid_len_out, issued_at_out=None, okr: Keyring | None = None,
+                     stream=None) -> None:
+    """status[i] (device uint8) = QUIC_TOKEN_* of the token Initial i carries;
+    odcid_out [n*20], odcid_len_out [n] and issued_at_out (uint32, optional)
+    are written for OK and EXPIRED.  okr: wire datagrams, as quic_retry."""
+    out = (_ptr(status), _ptr(odcid_out), _ptr(odcid_len_out), _ptr(issued_at_out), stream)
+    if okr is None:
+        _check(lib().sqobfs_quic_retry_check(ctx.handle, ctypes.byref(batch), ctypes.byref(args),
+                                             *out), "sqobfs_quic_retry_check")
+    else:
+        _check(lib().sqobfs_quic_retry_check_salamander(ctx.handle, okr.handle, ctypes.byref(batch),
+                                                        ctypes.byref(args), *out),
+               "sqobfs_quic_retry_check_salamander")
