@@ -812,6 +812,98 @@ int sqobfs_quic_retry_check_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *ok
                                        uint32_t *issued_at_out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Stateless resets on the device (RFC 9000 10.3).  New symbols only: no
+ * struct above changes layout, so SQOBFS_ABI_VERSION stays as it is.
+ *
+ * A route call's UNKNOWN class holds short-header datagrams whose connection
+ * id is not in the map: what a peer keeps sending after this endpoint
+ * restarted or dropped the connection.  The side that lost the state answers
+ * each with a Stateless Reset (sqobfs_quic_reset); the side that still has
+ * state recognises one by the last 16 bytes of a datagram it cannot place
+ * otherwise (sqobfs_quic_reset_match: the UNKNOWN slice, or packets whose open
+ * returned SQOBFS_QUIC_EAUTH).  Both are stateless per datagram; under
+ * Hysteria2 neither is readable before the Salamander layer is off.
+ *
+ * "Packet" below is the datagram, or for a _salamander call the datagram
+ * after its 8 salt bytes, de-obfuscated; L is the packet's length.
+ *
+ * The reset built for datagram i:
+ *   - first byte with 0x80 set or 0x40 clear: out_len[i] = SQOBFS_QUIC_EHEADER,
+ *     nothing written (the peer of a long-header stray holds no token yet);
+ *   - else L < 22 (under Salamander also: no packet byte at all): out_len[i] =
+ *     SQOBFS_QUIC_ESHORT, nothing written.  A reset is at least 21 bytes and
+ *     smaller than its trigger (10.3.3), which is how reset loops end;
+ *   - else R = min(reset_len, L - 1), out_len[i] = R, and the output is
+ *       filler[0 .. R - 16) || token16,  byte 0 forced to (b & 0x3F) | 0x40
+ *     token16 = HMAC-SHA256(key, packet[1 .. 1 + cid_len))[0..16), quic-go's
+ *       GetStatelessResetToken: tokens a quic-go host advertised under `key`
+ *       and resets sent here agree;
+ *     filler  = ChaCha20 (the RFC 8439 block function) under the context's
+ *       salt key, nonce "sqsr" || le64(seq), block counter i.  seq is the
+ *       launch sequence number that sqobfs_salt_seq reports and
+ *       sqobfs_salt_key sets: a reset call takes the current value and
+ *       increments it once.  The prefix differs from the device salts'
+ *       "sqob", so the two never share a (key, nonce) pair.
+ *   _salamander writes salt[i] || reset ^ BLAKE2b-256(psk || salt[i]) and
+ *   out_len[i] = R + 8, as sqobfs_quic_retry_salamander wraps its output.
+ * Rate-limiting resets is the caller's job (10.3.3). */
+#define SQOBFS_QUIC_RESET_MIN 21u /* RFC 9000 10.3: 5 unpredictable bytes + the token */
+#define SQOBFS_QUIC_RESET_MAX 80u
+typedef struct sqobfs_quic_reset_args {
+  uint8_t key[32];    /* host: the endpoint's static stateless-reset key */
+  uint32_t cid_len;   /* 1..20: the length of the ids this endpoint issues */
+  uint32_t reset_len; /* 21..80: the length of a reset when the trigger allows it */
+} sqobfs_quic_reset_args;
+
+/* b supplies n, in, in_off, in_len, out, out_off and out_len (each output
+ * reset_len bytes of room, + 8 under Salamander; out disjoint from in);
+ * b->pn_offset, pn, key_id, pn_out and flags must be NULL / 0.  The input is
+ * not modified.  One kernel is queued on `stream`; the calls do not wait.
+ * SQ_EINVAL before anything is launched: a NULL argument or required pointer,
+ * cid_len or reset_len out of range, those fields of b not NULL / 0, salt
+ * NULL; okr as sqobfs_quic_route_salamander refuses it. */
+int sqobfs_quic_reset(sqobfs_ctx *ctx, const sqobfs_quic_batch *b,
+                      const sqobfs_quic_reset_args *a, void *stream);
+int sqobfs_quic_reset_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                                 const sqobfs_quic_batch *b, const sqobfs_quic_reset_args *a,
+                                 const uint8_t *salt /* [n*8] device */, void *stream);
+
+/* The peer's reset tokens: one per connection id it issues (the
+ * stateless_reset_token transport parameter, NEW_CONNECTION_ID frames).  They
+ * live in a second table inside the connection-id map, allocated at the first
+ * update (a map that never gets a token costs what it did before), of the same
+ * size and slot form as the first.  Semantics are sqobfs_quic_cidmap_update's:
+ * ops in order, an insert of a present token re-maps it, removal of an absent
+ * one is a no-op, at most max_cids tokens; more than that, or a conn >= conns
+ * that is not the REMOVE value, returns SQ_EINVAL and changes nothing.  The
+ * changed span is copied to the device on `stream`; returns when the copy has
+ * completed.  These keys are the peer's choice, not this endpoint's, so the
+ * table's hash is seeded per map with random bytes drawn at creation. */
+typedef struct sqobfs_quic_reset_op {
+  uint8_t token[16];
+  uint32_t conn; /* or SQOBFS_QUIC_CID_REMOVE */
+} sqobfs_quic_reset_op;
+int sqobfs_quic_cidmap_update_reset(sqobfs_ctx *ctx, sqobfs_quic_cidmap *m, uint32_t n,
+                                    const sqobfs_quic_reset_op *ops, void *stream);
+
+/* b supplies n, in, in_off and in_len; everything else in b must be NULL / 0.
+ * conn_out[i] (device, [n]) = the connection whose token equals the packet's
+ * last 16 bytes; SQOBFS_QUIC_NOCONN for a first byte with 0x80 set, a packet
+ * of fewer than 21 bytes, a token that is not in the map, or a map that never
+ * had one.  A slot's 16 bytes are always compared whole.  The number of
+ * matches is added to *hits (device, optional; the caller zeroes it), so the
+ * host reads four bytes to learn whether conn_out is worth reading.  The input
+ * is not modified.  One kernel is queued on `stream`; the calls do not wait.
+ * SQ_EINVAL as sqobfs_quic_route(_salamander) gives it, and for conn_out
+ * NULL. */
+int sqobfs_quic_reset_match(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
+                            const sqobfs_quic_batch *b, uint32_t *conn_out /* [n] device */,
+                            uint32_t *hits /* device, optional */, void *stream);
+int sqobfs_quic_reset_match_salamander(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
+                                       const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
+                                       uint32_t *conn_out, uint32_t *hits, void *stream);
+
+/* ------------------------------------------------------------------------
  * Several GPUs in one process (packets are independent, so a
  * batch shards into contiguous ranges with no exchange at all).
  */

@@ -1855,92 +1855,137 @@ int sqobfs_quic_initial_seal_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *o
 
 // ---- routing received datagrams: the connection-id map and the route call
 extern "C++" {
-// Host-authoritative: `host` is the table (linear probing, a slot with conn ==
-// kQuicNoConn is empty, removal by backward shift), `dev` its image.  Slots
-// [dirty_lo, dirty_hi) differ from the image until cid_flush copies them.
+namespace {
+// the key words of a slot and the table's hash of them (sq_internal.h)
+inline uint32_t (&slot_key(sq::CidSlot &s))[sq::kCidWords] { return s.cid; }
+inline uint32_t (&slot_key(sq::ResetSlot &s))[sq::kResetWords] { return s.token; }
+inline uint32_t slot_hash(const uint32_t (&k)[sq::kCidWords], const uint32_t (&)[2]) {
+  return sq::cid_hash(k);
+}
+inline uint32_t slot_hash(const uint32_t (&k)[sq::kResetWords], const uint32_t (&seed)[2]) {
+  return sq::reset_hash(k, seed);
+}
+
+// Host-authoritative open-addressing table of 32-byte slots keyed by W words:
+// `host` is the table (linear probing, a slot with conn == kQuicNoConn is
+// empty, removal by backward shift), `dev` its image.  Slots [dirty_lo,
+// dirty_hi) differ from the image until flush copies them.  span: the longest
+// distance from its home slot that an entry has been put at.
+template <class Slot, uint32_t W>
+struct SlotTable {
+  struct Key {
+    uint32_t w[W];
+  };
+  std::vector<Slot> host;
+  uint32_t mask = 0, live = 0, span = 0;
+  uint32_t dirty_lo = 0, dirty_hi = 0;
+  uint32_t seed[2] = {0u, 0u};
+  Slot *dev = nullptr;
+
+  void touch(uint32_t s) {
+    if (dirty_lo == dirty_hi) {
+      dirty_lo = s;
+      dirty_hi = s + 1;
+    } else {
+      dirty_lo = std::min(dirty_lo, s);
+      dirty_hi = std::max(dirty_hi, s + 1);
+    }
+  }
+  uint32_t home(const uint32_t (&k)[W]) const { return slot_hash(k, seed) & mask; }
+
+  // the key's slot, or the empty slot that ends its probe chain
+  uint32_t find(const Key &k) {
+    uint32_t s = home(k.w);
+    while (host[s].conn != sq::kQuicNoConn && memcmp(slot_key(host[s]), k.w, sizeof k.w) != 0)
+      s = (s + 1) & mask;
+    return s;
+  }
+
+  // Maps the key to conn (kQuicNoConn: removes it) and returns what it was
+  // mapped to before (kQuicNoConn: absent).
+  uint32_t set(const Key &k, uint32_t conn) {
+    uint32_t i = find(k);
+    const uint32_t prev = host[i].conn;
+    if (conn != sq::kQuicNoConn) {
+      memcpy(slot_key(host[i]), k.w, sizeof k.w);
+      host[i].conn = conn;
+      live += prev == sq::kQuicNoConn;
+      span = std::max(span, (i - home(k.w)) & mask);
+      touch(i);
+      return prev;
+    }
+    if (prev == sq::kQuicNoConn) return prev;
+    // backward shift: a later entry of the chain moves into the hole unless
+    // its home slot lies (cyclically) after the hole
+    for (uint32_t j = i;;) {
+      j = (j + 1) & mask;
+      if (host[j].conn == sq::kQuicNoConn) break;
+      const uint32_t h = home(slot_key(host[j]));
+      if (i <= j ? (i < h && h <= j) : (i < h || h <= j)) continue;
+      host[i] = host[j];
+      touch(i);
+      i = j;
+    }
+    memset(&host[i], 0, sizeof host[i]);
+    host[i].conn = sq::kQuicNoConn;
+    touch(i);
+    live--;
+    return prev;
+  }
+
+  // `slots` (a power of two) empty slots; the whole image is dirty
+  void clear(uint32_t slots) {
+    Slot empty;
+    memset(&empty, 0, sizeof empty);
+    empty.conn = sq::kQuicNoConn;
+    host.assign(slots, empty);
+    mask = slots - 1;
+    live = span = 0;
+    dirty_lo = 0;
+    dirty_hi = slots;
+  }
+
+  // the slots that changed -> the device image, waited for
+  int flush(hipStream_t s) {
+    if (dirty_lo == dirty_hi) return SQ_OK;
+    hipError_t e = hipMemcpyAsync(dev + dirty_lo, host.data() + dirty_lo,
+                                  sizeof(Slot) * (dirty_hi - dirty_lo), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) dirty_lo = dirty_hi = 0;
+    return hip_status(e);
+  }
+
+  // ops in order, remembering what each key was mapped to: an update that
+  // leaves more than max_live keys is taken back op by op (the keys' slots may
+  // then differ from before, their connections do not).  True: it overflowed.
+  template <class Op, class KeyOf>
+  bool apply(uint32_t n, const Op *ops, uint32_t max_live, KeyOf key_of) {
+    std::vector<uint32_t> prev(n);
+    uint32_t done = 0;
+    for (; done < n; done++) {
+      prev[done] = set(key_of(ops[done]), ops[done].conn);
+      if (live > max_live) break;
+    }
+    if (done == n) return false;
+    for (uint32_t i = done + 1; i-- > 0;) (void)set(key_of(ops[i]), prev[i]);
+    return true;
+  }
+};
+using CidTable = SlotTable<sq::CidSlot, sq::kCidWords>;
+using ResetTable = SlotTable<sq::ResetSlot, sq::kResetWords>;
+}  // namespace
+
+// ids: connection ids -> connections; toks: the peer's stateless-reset tokens
+// -> connections (sq_quic_reset.hip), empty and without a device image until
+// the first sqobfs_quic_cidmap_update_reset.
 struct sqobfs_quic_cidmap {
   sqobfs_ctx *ctx = nullptr;
   mutable KeyringUses uses;
-  uint32_t conns = 0, max_cids = 0, cid_len = 0, mask = 0, live = 0;
-  std::vector<sq::CidSlot> host;
-  uint32_t dirty_lo = 0, dirty_hi = 0;
-  sq::CidSlot *dev = nullptr;
+  uint32_t conns = 0, max_cids = 0, cid_len = 0;
+  CidTable ids;
+  ResetTable toks;
   uint64_t *pn_state = nullptr;  // device [conns][3]
 };
-
-namespace {
-struct CidKey {
-  uint32_t w[sq::kCidWords];
-};
-
-CidKey cid_key(const uint8_t *cid, uint32_t len) {
-  uint8_t b[4 * sq::kCidWords] = {0};
-  memcpy(b, cid, len);
-  CidKey k;
-  for (uint32_t j = 0; j < sq::kCidWords; j++) k.w[j] = le32(b + 4 * j);
-  return k;
-}
-
-void cid_touch(sqobfs_quic_cidmap *m, uint32_t s) {
-  if (m->dirty_lo == m->dirty_hi) {
-    m->dirty_lo = s;
-    m->dirty_hi = s + 1;
-  } else {
-    m->dirty_lo = std::min(m->dirty_lo, s);
-    m->dirty_hi = std::max(m->dirty_hi, s + 1);
-  }
-}
-
-// the key's slot, or the empty slot that ends its probe chain
-uint32_t cid_find(const sqobfs_quic_cidmap *m, const CidKey &k) {
-  uint32_t s = sq::cid_hash(k.w) & m->mask;
-  while (m->host[s].conn != sq::kQuicNoConn && memcmp(m->host[s].cid, k.w, sizeof k.w) != 0)
-    s = (s + 1) & m->mask;
-  return s;
-}
-
-// Maps the key to conn (kQuicNoConn: removes it) and returns what it was
-// mapped to before (kQuicNoConn: absent).
-uint32_t cid_set(sqobfs_quic_cidmap *m, const CidKey &k, uint32_t conn) {
-  uint32_t i = cid_find(m, k);
-  const uint32_t prev = m->host[i].conn;
-  if (conn != sq::kQuicNoConn) {
-    memcpy(m->host[i].cid, k.w, sizeof k.w);
-    m->host[i].conn = conn;
-    m->live += prev == sq::kQuicNoConn;
-    cid_touch(m, i);
-    return prev;
-  }
-  if (prev == sq::kQuicNoConn) return prev;
-  // backward shift: a later entry of the chain moves into the hole unless
-  // its home slot lies (cyclically) after the hole
-  for (uint32_t j = i;;) {
-    j = (j + 1) & m->mask;
-    if (m->host[j].conn == sq::kQuicNoConn) break;
-    const uint32_t home = sq::cid_hash(m->host[j].cid) & m->mask;
-    if (i <= j ? (i < home && home <= j) : (i < home || home <= j)) continue;
-    m->host[i] = m->host[j];
-    cid_touch(m, i);
-    i = j;
-  }
-  memset(&m->host[i], 0, sizeof m->host[i]);
-  m->host[i].conn = sq::kQuicNoConn;
-  cid_touch(m, i);
-  m->live--;
-  return prev;
-}
-
-// the slots that changed -> the device image, waited for
-int cid_flush(sqobfs_quic_cidmap *m, hipStream_t s) {
-  if (m->dirty_lo == m->dirty_hi) return SQ_OK;
-  hipError_t e = hipMemcpyAsync(m->dev + m->dirty_lo, m->host.data() + m->dirty_lo,
-                                sizeof(sq::CidSlot) * (m->dirty_hi - m->dirty_lo),
-                                hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e == hipSuccess) m->dirty_lo = m->dirty_hi = 0;
-  return hip_status(e);
-}
-}  // namespace
 }  // extern "C++"
 
 int sqobfs_quic_cidmap_create(sqobfs_ctx *ctx, uint32_t conns, uint32_t max_cids, uint32_t cid_len,
@@ -1959,22 +2004,26 @@ int sqobfs_quic_cidmap_create(sqobfs_ctx *ctx, uint32_t conns, uint32_t max_cids
   m->cid_len = cid_len;
   uint32_t slots = 4;  // (an update holds max_cids + 1 ids before it is refused: never full)
   while (slots < 2 * max_cids) slots *= 2;
-  m->mask = slots - 1;
-  sq::CidSlot empty;
-  memset(&empty, 0, sizeof empty);
-  empty.conn = sq::kQuicNoConn;
-  m->host.assign(slots, empty);
-  m->dirty_hi = slots;  // the whole image, once
+  m->ids.clear(slots);  // the whole image, once
+  // the token table's seed: the peer picks those keys (sq_internal.h reset_hash)
+  for (size_t got = 0; got < sizeof m->toks.seed;) {
+    const ssize_t r = getrandom((uint8_t *)m->toks.seed + got, sizeof m->toks.seed - got, 0);
+    if (r < 0) {  // (as sqobfs_open)
+      delete m;
+      return SQ_EDEVICE;
+    }
+    got += (size_t)r;
+  }
   hipStream_t s = ctx->stream;
   const size_t pbytes = sizeof(uint64_t) * 3 * conns;
-  hipError_t e = tab_alloc((void **)&m->dev, sizeof(sq::CidSlot) * slots, s);
+  hipError_t e = tab_alloc((void **)&m->ids.dev, sizeof(sq::CidSlot) * slots, s);
   if (e == hipSuccess) e = tab_alloc((void **)&m->pn_state, pbytes, s);
   if (e == hipSuccess) e = hipMemsetAsync(m->pn_state, 0, pbytes, s);
   int st = hip_status(e);
-  if (st == SQ_OK) st = cid_flush(m, s);
+  if (st == SQ_OK) st = m->ids.flush(s);
   if (st != SQ_OK) {
     (void)hipStreamSynchronize(s);
-    tab_free_async(m->dev, s);
+    tab_free_async(m->ids.dev, s);
     tab_free_async(m->pn_state, s);
     (void)hipStreamSynchronize(s);
     delete m;
@@ -1988,7 +2037,8 @@ void sqobfs_quic_cidmap_destroy(sqobfs_quic_cidmap *m) {
   if (!m) return;
   DeviceScope ds_(m->ctx->device);
   m->uses.fence(m->ctx->rel);  // as sqobfs_keyring_destroy: stream-ordered, no wait
-  tab_free_async(m->dev, m->ctx->rel);
+  tab_free_async(m->ids.dev, m->ctx->rel);
+  tab_free_async(m->toks.dev, m->ctx->rel);
   tab_free_async(m->pn_state, m->ctx->rel);
   delete m;
 }
@@ -2002,19 +2052,43 @@ int sqobfs_quic_cidmap_update(sqobfs_ctx *ctx, sqobfs_quic_cidmap *m, uint32_t n
     if (ops[i].conn >= m->conns && ops[i].conn != SQOBFS_QUIC_CID_REMOVE) return SQ_EINVAL;
   DeviceScope ds_(ctx->device);
   if (ds_.status != SQ_OK) return ds_.status;
-  // in order, remembering what each id was mapped to: an update that
-  // overflows is taken back op by op (the ids' slots may then differ from
-  // before, their connections do not)
-  std::vector<uint32_t> prev(n);
-  uint32_t done = 0;
-  for (; done < n; done++) {
-    prev[done] = cid_set(m, cid_key(ops[done].cid, m->cid_len), ops[done].conn);
-    if (m->live > m->max_cids) break;
+  const uint32_t cl = m->cid_len;
+  const bool overflow = m->ids.apply(n, ops, m->max_cids, [cl](const sqobfs_quic_cid_op &op) {
+    uint8_t b[4 * sq::kCidWords] = {0};  // zero-padded, little-endian words
+    memcpy(b, op.cid, cl);
+    CidTable::Key k;
+    for (uint32_t j = 0; j < sq::kCidWords; j++) k.w[j] = le32(b + 4 * j);
+    return k;
+  });
+  const int st = m->ids.flush(pick_stream(ctx, stream));
+  return overflow ? SQ_EINVAL : st;
+}
+
+int sqobfs_quic_cidmap_update_reset(sqobfs_ctx *ctx, sqobfs_quic_cidmap *m, uint32_t n,
+                                    const sqobfs_quic_reset_op *ops, void *stream) {
+  if (!ctx || !m || m->ctx != ctx) return SQ_EINVAL;
+  if (n == 0) return SQ_OK;
+  if (!ops) return SQ_EINVAL;
+  for (uint32_t i = 0; i < n; i++)
+    if (ops[i].conn >= m->conns && ops[i].conn != SQOBFS_QUIC_CID_REMOVE) return SQ_EINVAL;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  hipStream_t s = pick_stream(ctx, stream);
+  if (!m->toks.dev) {  // the first tokens: the table and its image, sized as the ids'
+    const uint32_t slots = m->ids.mask + 1;
+    const hipError_t e = tab_alloc((void **)&m->toks.dev, sizeof(sq::ResetSlot) * slots, s);
+    if (e != hipSuccess) {
+      m->toks.dev = nullptr;
+      return hip_status(e);
+    }
+    m->toks.clear(slots);
   }
-  const bool overflow = done < n;
-  if (overflow)
-    for (uint32_t i = done + 1; i-- > 0;) (void)cid_set(m, cid_key(ops[i].cid, m->cid_len), prev[i]);
-  const int st = cid_flush(m, pick_stream(ctx, stream));
+  const bool overflow = m->toks.apply(n, ops, m->max_cids, [](const sqobfs_quic_reset_op &op) {
+    ResetTable::Key k;
+    for (uint32_t j = 0; j < sq::kResetWords; j++) k.w[j] = le32(op.token + 4 * j);
+    return k;
+  });
+  const int st = m->toks.flush(s);
   return overflow ? SQ_EINVAL : st;
 }
 
@@ -2069,7 +2143,7 @@ static int quic_route_launch(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
   rp.in_off = b->in_off;
   rp.in_len = b->in_len;
   rp.out_off = b->out_off;
-  rp.slots = m->dev;
+  rp.slots = m->ids.dev;
   rp.pn_state = m->pn_state;
   rp.r_cls = r->cls;
   rp.r_count = r->count;
@@ -2083,7 +2157,7 @@ static int quic_route_launch(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
   rp.r_conn = r->conn;
   rp.n = b->n;
   rp.nwg = (uint32_t)(((uint64_t)b->n + sq::kRouteBlock - 1) / sq::kRouteBlock);
-  rp.slot_mask = m->mask;
+  rp.slot_mask = m->ids.mask;
   rp.cid_len = m->cid_len;
   if (okr) {  // entry 0 of the keyring's device table, as the Initial key kernel reads it
     rp.obfs = 1;
@@ -2284,6 +2358,126 @@ int sqobfs_quic_retry_check_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *ok
   if (!okr) return SQ_EINVAL;
   return quic_retry_launch(1, ctx, okr, b, a, nullptr, status, odcid_out, odcid_len_out,
                            issued_at_out, stream);
+}
+
+// ---- stateless resets (sq_quic_reset.hip)
+extern "C++" {
+namespace {
+// "sqsr" || le64(seq): the ChaCha20 nonce of one reset call's filler
+constexpr uint32_t kResetDomain = 0x72737173u;  // bytes 's' 'q' 's' 'r'
+
+// st = the SHA-256 state after the block key ^ pad (HMAC's two midstates)
+void hmac_midstate(const uint8_t key[32], uint8_t pad, uint32_t st[8]) {
+  static const uint32_t iv[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                                 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+  uint32_t m[16];
+  for (int j = 0; j < 16; j++) {
+    uint32_t w = 0;
+    for (int k = 0; k < 4; k++) w = (w << 8) | (uint8_t)((j < 8 ? key[4 * j + k] : 0) ^ pad);
+    m[j] = w;
+  }
+  memcpy(st, iv, sizeof iv);
+  sq::cpu::s2_compress(st, m);
+}
+
+// the batch fields that both reset calls refuse, and the fused form's keyring
+bool reset_batch_ok(sqobfs_ctx *ctx, const sqobfs_keyring *okr, const sqobfs_quic_batch *b) {
+  if (!ctx || !b || b->flags || b->pn_offset || b->pn || b->key_id || b->pn_out) return false;
+  if (okr && (okr->ctx != ctx || okr->kind != SQOBFS_SALAMANDER)) return false;
+  return b->in && b->in_off && b->in_len;
+}
+
+int quic_reset_launch(sqobfs_ctx *ctx, const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
+                      const sqobfs_quic_reset_args *a, const uint8_t *salt, void *stream) {
+  if (!reset_batch_ok(ctx, okr, b) || !a || (okr && !salt)) return SQ_EINVAL;
+  if (a->cid_len < 1 || a->cid_len > 4 * sq::kCidWords || a->reset_len < SQOBFS_QUIC_RESET_MIN ||
+      a->reset_len > SQOBFS_QUIC_RESET_MAX)
+    return SQ_EINVAL;
+  if (!b->out || !b->out_off || !b->out_len) return SQ_EINVAL;
+  if (b->n == 0) return SQ_OK;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  sq::QResetParams rp;
+  memset(&rp, 0, sizeof rp);
+  rp.in = b->in;
+  rp.in_off = b->in_off;
+  rp.in_len = b->in_len;
+  rp.out = b->out;
+  rp.out_off = b->out_off;
+  rp.out_len = b->out_len;
+  rp.salt = salt;
+  if (okr) rp.opsk = okr->table;
+  rp.n = b->n;
+  rp.cid_len = a->cid_len;
+  rp.reset_len = a->reset_len;
+  hmac_midstate(a->key, 0x36, rp.im);
+  hmac_midstate(a->key, 0x5c, rp.om);
+  uint64_t seq;
+  sq_salt_take(ctx, rp.fkey, &seq);
+  rp.fnonce[0] = kResetDomain;
+  rp.fnonce[1] = (uint32_t)seq;
+  rp.fnonce[2] = (uint32_t)(seq >> 32);
+  hipStream_t s = pick_stream(ctx, stream);
+  const int st = sq_launch_quic_reset(0, okr != nullptr, &rp, s);
+  if (st == SQ_OK && okr) okr->uses.note(s);
+  return st;
+}
+
+int quic_reset_match_launch(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
+                            const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
+                            uint32_t *conn_out, uint32_t *hits, void *stream) {
+  if (!reset_batch_ok(ctx, okr, b) || !m || m->ctx != ctx || !conn_out) return SQ_EINVAL;
+  if (b->out || b->out_off || b->out_len) return SQ_EINVAL;
+  if (b->n == 0) return SQ_OK;
+  DeviceScope ds_(ctx->device);
+  if (ds_.status != SQ_OK) return ds_.status;
+  sq::QResetParams rp;
+  memset(&rp, 0, sizeof rp);
+  rp.in = b->in;
+  rp.in_off = b->in_off;
+  rp.in_len = b->in_len;
+  if (okr) rp.opsk = okr->table;
+  rp.slots = m->toks.dev;  // (NULL until the first token: every answer is NOCONN)
+  rp.conn_out = conn_out;
+  rp.hits = hits;
+  rp.n = b->n;
+  rp.slot_mask = m->toks.mask;
+  rp.span = m->toks.span;
+  memcpy(rp.seed, m->toks.seed, sizeof rp.seed);
+  hipStream_t s = pick_stream(ctx, stream);
+  const int st = sq_launch_quic_reset(1, okr != nullptr, &rp, s);
+  if (st == SQ_OK) {
+    m->uses.note(s);
+    if (okr) okr->uses.note(s);
+  }
+  return st;
+}
+}  // namespace
+}  // extern "C++"
+
+int sqobfs_quic_reset(sqobfs_ctx *ctx, const sqobfs_quic_batch *b,
+                      const sqobfs_quic_reset_args *a, void *stream) {
+  return quic_reset_launch(ctx, nullptr, b, a, nullptr, stream);
+}
+
+int sqobfs_quic_reset_salamander(sqobfs_ctx *ctx, const sqobfs_keyring *okr,
+                                 const sqobfs_quic_batch *b, const sqobfs_quic_reset_args *a,
+                                 const uint8_t *salt, void *stream) {
+  if (!okr || !salt) return SQ_EINVAL;
+  return quic_reset_launch(ctx, okr, b, a, salt, stream);
+}
+
+int sqobfs_quic_reset_match(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
+                            const sqobfs_quic_batch *b, uint32_t *conn_out, uint32_t *hits,
+                            void *stream) {
+  return quic_reset_match_launch(ctx, m, nullptr, b, conn_out, hits, stream);
+}
+
+int sqobfs_quic_reset_match_salamander(sqobfs_ctx *ctx, const sqobfs_quic_cidmap *m,
+                                       const sqobfs_keyring *okr, const sqobfs_quic_batch *b,
+                                       uint32_t *conn_out, uint32_t *hits, void *stream) {
+  if (!okr) return SQ_EINVAL;
+  return quic_reset_match_launch(ctx, m, okr, b, conn_out, hits, stream);
 }
 
 size_t sqobfs_host_staging_bytes(const sqobfs_ctx *ctx) { return ctx ? ctx->pinned_cap : 0; }

@@ -359,7 +359,63 @@ struct QRetryParams {
   uint32_t ekj0[4];          // E_K(J0) of the Retry integrity key, little-endian words
 };
 
+// Stateless resets (sq_quic_reset.hip).  One slot of the map's second table:
+// a reset token the peer advertised, as little-endian words, then its
+// connection.  32 bytes as CidSlot, so the host table code serves both.
+constexpr uint32_t kResetWords = 4;  // RFC 9000 10.3: 16 bytes
+struct alignas(16) ResetSlot {
+  uint32_t token[kResetWords];
+  uint32_t conn;
+  uint32_t pad[3];
+};
+static_assert(sizeof(ResetSlot) == 32, "ResetSlot layout");
+// That table's hash, the same on both sides.  Unlike connection ids these
+// keys are chosen by the peer, so the mixing of cid_hash starts from and ends
+// with a seed the map draws at creation: without it a peer cannot aim its
+// tokens at one probe chain.
+SQ_HD inline uint32_t reset_hash(const uint32_t (&t)[kResetWords], const uint32_t (&seed)[2]) {
+  uint32_t h = seed[0];
+  for (uint32_t j = 0; j < kResetWords; j++) {
+    h = (h ^ t[j]) * 0x85EBCA6Bu;
+    h ^= h >> 15;
+  }
+  h = (h ^ seed[1]) * 0xC2B2AE35u;
+  return h ^ (h >> 16);
+}
+
+// One launch of either reset kernel.  build: every datagram shares the HMAC
+// key, which travels as its two pad midstates (im, om: SHA-256 state words,
+// made once per call on the host), and the filler's ChaCha20 key and nonce.
+// match: the token table, its seed and `span`, the longest distance from its
+// home slot that any token of the table has had: a probe reads span + 1 slots.
+struct QResetParams {
+  const uint8_t *in;
+  const uint64_t *in_off;
+  const uint32_t *in_len;
+  uint8_t *out;              // build
+  const uint64_t *out_off;
+  uint32_t *out_len;
+  const uint8_t *salt;       // [n * 8] fused build: the resets' salts
+  const PskEntry *opsk;      // fused: the Salamander keyring's device entry 0
+  const ResetSlot *slots;    // match: [slot_mask + 1], or NULL (no token yet)
+  uint32_t *conn_out;        // match: [n]
+  uint32_t *hits;            // match: or NULL
+  uint32_t n;
+  uint32_t cid_len;
+  uint32_t reset_len;
+  uint32_t slot_mask;
+  uint32_t span;
+  uint32_t seed[2];
+  uint32_t im[8], om[8];
+  uint32_t fkey[8];
+  uint32_t fnonce[3];        // "sqsr" || le64(seq)
+};
+constexpr uint32_t kResetBlock = 256;  // datagrams per workgroup
+
 }  // namespace sq
+
+// launcher implemented in sq_quic_reset.hip: quic_reset<obfs> / quic_reset_match<obfs>
+extern "C" int sq_launch_quic_reset(int match, int obfs, const sq::QResetParams *rp, void *stream);
 
 // launcher implemented in sq_quic_retry.hip: quic_retry<check, obfs>
 extern "C" int sq_launch_quic_retry(int check, int obfs, const sq::QRetryParams *rp, void *stream);

@@ -156,6 +156,20 @@ class QuicRetryArgs(ctypes.Structure):
                 ("token", ctypes.c_void_p), ("token_len", ctypes.c_void_p)]
 
 
+QUIC_RESET_MIN, QUIC_RESET_MAX = 21, 80  # SQOBFS_QUIC_RESET_*
+
+
+class QuicResetArgs(ctypes.Structure):
+    """sqobfs_quic_reset_args."""
+    _fields_ = [("key", ctypes.c_uint8 * 32), ("cid_len", ctypes.c_uint32),
+                ("reset_len", ctypes.c_uint32)]
+
+
+class QuicResetOp(ctypes.Structure):
+    """sqobfs_quic_reset_op: map the peer's reset token to conn, or remove it."""
+    _fields_ = [("token", ctypes.c_uint8 * 16), ("conn", ctypes.c_uint32)]
+
+
 class UdpView(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint32), ("base", ctypes.c_void_p), ("off", ctypes.c_void_p),
                 ("len", ctypes.c_void_p), ("fd_index", ctypes.c_void_p),
@@ -278,6 +292,13 @@ def load(path: str) -> ctypes.CDLL:
         L.sqobfs_quic_retry_salamander.argtypes = [vp, vp, qb, ra, vp, vp]
         L.sqobfs_quic_retry_check.argtypes = [vp, qb, ra, vp, vp, vp, vp, vp]
         L.sqobfs_quic_retry_check_salamander.argtypes = [vp, vp, qb, ra, vp, vp, vp, vp, vp]
+    if hasattr(L, "sqobfs_quic_reset"):  # (absent from earlier builds)
+        qb, sa = ctypes.POINTER(QuicBatch), ctypes.POINTER(QuicResetArgs)
+        L.sqobfs_quic_reset.argtypes = [vp, qb, sa, vp]
+        L.sqobfs_quic_reset_salamander.argtypes = [vp, vp, qb, sa, vp, vp]
+        L.sqobfs_quic_cidmap_update_reset.argtypes = [vp, vp, u32, vp, vp]
+        L.sqobfs_quic_reset_match.argtypes = [vp, vp, qb, vp, vp, vp]
+        L.sqobfs_quic_reset_match_salamander.argtypes = [vp, vp, vp, qb, vp, vp, vp]
     L.sqobfs_salt_key.argtypes = [vp, vp, ctypes.c_uint64]
     L.sqobfs_salt_seq.argtypes = [vp]
     L.sqobfs_salt_seq.restype = ctypes.c_uint64
@@ -1043,6 +1064,17 @@ class QuicCidMap:
         _check(lib().sqobfs_quic_cidmap_update(self.ctx.handle, self.handle, len(ops), arr,
                                                stream), "sqobfs_quic_cidmap_update")
 
+    def update_reset(self, ops: list[tuple[bytes, int]], stream=None) -> None:
+        """The peer's stateless-reset tokens, as update: (token16, conn) maps
+        the token, (token16, QUIC_CID_REMOVE) removes it."""
+        arr = (QuicResetOp * max(len(ops), 1))()
+        for a, (token, conn) in zip(arr, ops):
+            assert len(token) == 16
+            ctypes.memmove(a.token, token, 16)
+            a.conn = conn
+        _check(lib().sqobfs_quic_cidmap_update_reset(self.ctx.handle, self.handle, len(ops), arr,
+                                                     stream), "sqobfs_quic_cidmap_update_reset")
+
     def reset_pn(self, conns: list[int], stream=None) -> None:
         """The connection slots are reused: their packet numbers restart at 0."""
         idx = (ctypes.c_uint32 * max(len(conns), 1))(*conns)
@@ -1162,3 +1194,38 @@ def quic_retry_check(ctx: Context, batch: QuicBatch, args: QuicRetryArgs, status
         _check(lib().sqobfs_quic_retry_check_salamander(ctx.handle, okr.handle, ctypes.byref(batch),
                                                         ctypes.byref(args), *out),
                "sqobfs_quic_retry_check_salamander")
+
+
+def quic_reset(ctx: Context, batch: QuicBatch, key: bytes, cid_len: int, reset_len: int,
+               okr: Keyring | None = None, salt=None, stream=None) -> None:
+    """Build a stateless reset for every short-header datagram of the batch
+    (out_len: its length, or QUIC_EHEADER / QUIC_ESHORT): filler || token16,
+    token16 = HMAC-SHA256(key, the datagram's connection id)[:16].  okr: the
+    batch holds Hysteria2 wire datagrams and the resets leave as salt[i] ||
+    reset ^ key (salt: device uint8 [n*8])."""
+    assert len(key) == 32
+    a = QuicResetArgs((ctypes.c_uint8 * 32)(*key), cid_len, reset_len)
+    if okr is None:
+        _check(lib().sqobfs_quic_reset(ctx.handle, ctypes.byref(batch), ctypes.byref(a), stream),
+               "sqobfs_quic_reset")
+    else:
+        _check(lib().sqobfs_quic_reset_salamander(ctx.handle, okr.handle, ctypes.byref(batch),
+                                                  ctypes.byref(a), _ptr(salt), stream),
+               "sqobfs_quic_reset_salamander")
+
+
+def quic_reset_match(ctx: Context, cmap: QuicCidMap, batch: QuicBatch, conn_out, hits=None,
+                     okr: Keyring | None = None, stream=None) -> None:
+    """conn_out[i] (device uint32) = the connection whose reset token
+    (QuicCidMap.update_reset) is the datagram's last 16 bytes, else
+    QUIC_NOCONN; the number of matches is added to hits[0] (device uint32,
+    optional).  okr: wire datagrams, as quic_reset."""
+    if okr is None:
+        _check(lib().sqobfs_quic_reset_match(ctx.handle, cmap.handle, ctypes.byref(batch),
+                                             _ptr(conn_out), _ptr(hits), stream),
+               "sqobfs_quic_reset_match")
+    else:
+        _check(lib().sqobfs_quic_reset_match_salamander(ctx.handle, cmap.handle, okr.handle,
+                                                        ctypes.byref(batch), _ptr(conn_out),
+                                                        _ptr(hits), stream),
+               "sqobfs_quic_reset_match_salamander")
